@@ -5,6 +5,12 @@ B=256, C=6, T=256 synthetic batch with K=512 codebooks (BASELINE configs[1..3];
 configs/config.yaml architecture otherwise).  N>1: one process per GPU, plain data
 parallel (RCCL all-reduce of the flat gradient buffer, the reference's sync_codebook
 EMA all-reduce), weak scaling (global batch 256*N).  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times `--steps` steps and prints the line (`ms_per_step` =
+one timed step).  `--dump-outputs DIR` also writes what the last timed step computed as
+DIR/<name>.npy (same arguments -> same inputs, so two builds compare output for output).
+`--full` adds every other leg to the line: the roofline kernels, BASELINE configs[0], the
+CPU baseline, the sampler and each stage alone.
 """
 import argparse
 import copy
@@ -1126,11 +1132,59 @@ def dry_launch(args):
     dist.destroy_process_group()
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def _dump_sample(a, budget):
+    """`a` as a flat-or-shaped float array of at most `budget` bytes: the array itself, or
+    (larger ones) its elements at a fixed, seeded, sorted set of flat indices."""
+    import numpy as np
+    a = np.ascontiguousarray(a)
+    if a.dtype not in (np.float32, np.float64):
+        a = a.astype(np.float64 if a.dtype.itemsize > 4 else np.float32)
+    keep = budget // a.dtype.itemsize
+    if a.size <= keep:
+        return a
+    idx = np.sort(np.random.default_rng(0).choice(a.size, size=keep, replace=False))
+    return a.reshape(-1)[idx]
+
+
+def dump_outputs(path, tr, out1, out2):
+    """--dump-outputs DIR: what the last timed step returned and left behind, one
+    DIR/<name>.npy each (float32): every entry of the two stages' step dicts (losses,
+    perplexities), and the state the step updated in place -- each stage's flat parameter
+    buffer after its AdamW update and its floating-point buffers (EMA codebooks, BatchNorm
+    running statistics) in state_dict order.  At most DUMP_BUDGET_BYTES in all: an array
+    above its equal share is written as a fixed seeded sample of its elements."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {}
+    for stage, out in (("stage1", out1), ("stage2", out2)):
+        for k, v in out.items():
+            if torch.is_tensor(v):
+                arrays[f"{stage}.{k}"] = v.detach().float().cpu().numpy()
+    for stage, mod, opt in (("stage1", tr.s1, tr.opt1), ("stage2", tr.s2, tr.opt2)):
+        arrays[f"{stage}.params"] = opt.flat.detach().cpu().numpy()
+        bufs = [b.detach().reshape(-1).float().cpu() for b in mod.buffers()
+                if b.is_floating_point()]
+        if bufs:
+            arrays[f"{stage}.buffers"] = torch.cat(bufs).numpy()
+    share = DUMP_BUDGET_BYTES // len(arrays)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), _dump_sample(a, share))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every other leg: the roofline kernels, "
+                         "BASELINE configs[0], the CPU baseline, the sampler, each stage alone "
+                         "(each can be switched off with its --no-* flag)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-sampler", action="store_true")
@@ -1195,6 +1249,8 @@ def main():
         elapsed = max(rank_elapsed)
     loss1 = float(out1["loss"].detach().sum())
     loss2 = float(out2["loss"].detach())
+    if args.dump_outputs and rank == 0:  # before any --full leg moves the weights
+        dump_outputs(args.dump_outputs, tr, out1, out2)
 
     if rank == 0:
         value = world * args.steps / elapsed
@@ -1230,22 +1286,24 @@ def main():
                 res["rehearsal"] = True
                 res["parallelism_note"] = ("REHEARSAL: every rank on cuda:0 over gloo; not a "
                                            "multi-GPU measurement")
-        if not args.no_roofline:
+        # a plain run ends here; every further leg is behind --full
+        if args.full and not args.no_roofline:
             res["roofline"] = roofline_leg(device, res["ms_per_step"])
-        if not args.no_config0 and world == 1:  # (before the sampler: rank 0 only)
+        if args.full and not args.no_config0 and world == 1:  # (before the sampler: rank 0 only)
             res["config0"] = config0_leg(device, cpu=not args.no_cpu_baseline)
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             res["cpu_baseline"] = cpu_baseline_leg()
-    if not args.no_sampler:  # every rank: replicas sample concurrently at world > 1
+    sampler = args.full and not args.no_sampler
+    if sampler:  # every rank: replicas sample concurrently at world > 1
         samp = sampler_leg(tr, device, world=world)
     # each stage's optimizer step alone (graph-replayed; the reference trains them one after
     # the other), beside the concurrent joint step -- last, since its extra optimizer steps
     # move the weights, LR schedule, BN statistics and codebooks the sampler leg reads
     alone = None
-    if world == 1 and not args.eager and not args.no_stage_legs:
+    if args.full and world == 1 and not args.eager and not args.no_stage_legs:
         alone = {w: round(tr.stage_alone_ms(batch, w), 3) for w in ("stage1", "stage2")}
     if rank == 0:
-        if not args.no_sampler:
+        if sampler:
             res["sampler"] = samp
         if alone is not None:
             res["stage1_ms_per_step"] = alone["stage1"]

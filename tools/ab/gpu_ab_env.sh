@@ -8,7 +8,7 @@ if [ -n "$PRE" ]; then
   timeout -k 10 600 python -u -m pytest $PRE -x -q --timeout 180 --timeout-method thread > gpurun_out/pre_tests.log 2>&1
   rc=$?; tail -3 gpurun_out/pre_tests.log; [ $rc -eq 0 ] || exit $rc
 fi
-B="python bench.py --steps 50 --warmup 10 --no-sampler --no-roofline --no-config0 --no-cpu-baseline"
+B="python bench.py --full --steps 50 --warmup 10 --no-sampler --no-roofline --no-config0 --no-cpu-baseline"
 IFS=';' read -ra ALT <<< "$ENVS"
 for i in 1 2 3; do
   timeout -k 10 300 $B > gpurun_out/abe_def_$i.log 2>&1 || { tail -20 gpurun_out/abe_def_$i.log; exit 1; }

@@ -11,6 +11,6 @@ grep -E "FAILED|ERROR|passed|failed" gpurun_out/pytest_gpu.log | tail -30
 [ $rc -eq 0 ] || [ $rc -eq 1 ] || exit $rc
 [ -n "$SKIP_SMOKE" ] || { timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" \
   > gpurun_out/smoke.log 2>&1; src=$?; tail -5 gpurun_out/smoke.log; [ $src -eq 0 ] || exit $src; }
-[ -n "$SKIP_BENCH" ] || { timeout -k 10 600 python bench.py --steps ${BENCH_STEPS:-20} --warmup 5 \
+[ -n "$SKIP_BENCH" ] || { timeout -k 10 600 python bench.py --full --steps ${BENCH_STEPS:-20} --warmup 5 \
   ${BENCH_ARGS} > gpurun_out/bench.log 2>&1; brc=$?; tail -3 gpurun_out/bench.log; [ $brc -eq 0 ] || exit $brc; }
 exit $rc

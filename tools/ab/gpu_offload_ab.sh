@@ -1,5 +1,5 @@
 #!/bin/bash
-A="--no-sampler --no-roofline --no-config0 --no-cpu-baseline --steps 30 --warmup 5"
+A="--full --no-sampler --no-roofline --no-config0 --no-cpu-baseline --steps 30 --warmup 5"
 mkdir -p gpurun_out
 for O in "" grad "grad,vq"; do
   TVQ_STREAMS_OFFLOAD="$O" timeout -k 10 200 python bench.py $A > gpurun_out/offl.log 2>&1

@@ -6,7 +6,7 @@ mkdir -p gpurun_out
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 timeout -k 10 900 python -u -m pytest tests -x -q -m gpu --timeout 180 --timeout-method thread ${PYTEST_ARGS} > gpurun_out/pytest_gpu.log 2>&1
 rc=$?; tail -15 gpurun_out/pytest_gpu.log; [ $rc -eq 0 ] || exit $rc
-B="python bench.py --steps 50 --warmup 10 --no-sampler --no-roofline --no-config0 --no-cpu-baseline"
+B="python bench.py --full --steps 50 --warmup 10 --no-sampler --no-roofline --no-config0 --no-cpu-baseline"
 REL=t-vq-vae-trajgen_amd/lib_ab/libtvq_hip_relaxed.so
 for i in 1 2; do
   timeout -k 10 300 $B > gpurun_out/ab_strict_$i.log 2>&1 || { tail -20 gpurun_out/ab_strict_$i.log; exit 1; }

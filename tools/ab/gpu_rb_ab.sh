@@ -14,7 +14,7 @@ timeout -k 10 120 python tools/rb_timing.py > gpurun_out/rb_timing.txt 2>&1 || {
 timeout -k 10 200 python tools/resblock_bench.py > gpurun_out/rb_bench_new.txt 2>&1 || { tail -20 gpurun_out/rb_bench_new.txt; exit 1; }
 TVQ_HIP_LIB=$OLD timeout -k 10 200 python tools/resblock_bench.py > gpurun_out/rb_bench_old.txt 2>&1 || { tail -20 gpurun_out/rb_bench_old.txt; exit 1; }
 echo new; cat gpurun_out/rb_bench_new.txt; echo old; cat gpurun_out/rb_bench_old.txt
-B="python bench.py --steps 50 --warmup 10 --no-sampler --no-roofline --no-config0 --no-cpu-baseline"
+B="python bench.py --full --steps 50 --warmup 10 --no-sampler --no-roofline --no-config0 --no-cpu-baseline"
 for i in 1 2 3; do
   TVQ_HIP_LIB=$NEWLIB timeout -k 10 300 $B > gpurun_out/ab_new_$i.log 2>&1 || { tail -20 gpurun_out/ab_new_$i.log; exit 1; }
   echo "new $i $(grep -o '"ms_per_step": [0-9.]*' gpurun_out/ab_new_$i.log)"

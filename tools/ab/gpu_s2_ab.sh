@@ -13,7 +13,7 @@ for lib in t-vq-vae-trajgen_amd/lib/libtvq_hip.so $OLD; do
   TVQ_HIP_LIB=$lib timeout -k 10 200 python tools/conv_shapes_bench.py 0,2,3,19,20,21,22 > gpurun_out/s2_shapes.log 2>&1 || { tail -5 gpurun_out/s2_shapes.log; exit 1; }
   grep -v amdgpu.ids gpurun_out/s2_shapes.log
 done
-B="python bench.py --steps 50 --warmup 10 --no-sampler --no-roofline --no-config0 --no-cpu-baseline"
+B="python bench.py --full --steps 50 --warmup 10 --no-sampler --no-roofline --no-config0 --no-cpu-baseline"
 for i in 1 2 3; do
   timeout -k 10 300 $B > gpurun_out/ab_new_$i.log 2>&1 || { tail -20 gpurun_out/ab_new_$i.log; exit 1; }
   echo "new $i $(grep -o '"ms_per_step": [0-9.]*' gpurun_out/ab_new_$i.log)"

@@ -18,7 +18,7 @@ for c in "$NEW 0" "$OLD 0" "$NEW 1"; do
   TVQ_CONV_SMALL_F=$2 TVQ_HIP_LIB=$1 timeout -k 10 300 python tools/conv_shapes_bench.py > gpurun_out/sm_shapes.log 2>&1 || { tail -5 gpurun_out/sm_shapes.log; exit 1; }
   grep -v amdgpu.ids gpurun_out/sm_shapes.log
 done
-B="python bench.py --steps 50 --warmup 10 --no-sampler --no-roofline --no-config0 --no-cpu-baseline"
+B="python bench.py --full --steps 50 --warmup 10 --no-sampler --no-roofline --no-config0 --no-cpu-baseline"
 for i in 1 2; do
   for c in "$NEW 0" "$OLD 0" "$NEW 1"; do
     set -- $c

@@ -10,7 +10,7 @@ for rg in 0 4 3 2; do
   TVQ_VQ_RG=$rg timeout -k 10 120 python tools/roofline_only.py vqassign > gpurun_out/vq_leg.log 2>&1 || { tail -5 gpurun_out/vq_leg.log; exit 1; }
   echo "rg=$rg $(grep -o '"avg_launch_us": [0-9.]*' gpurun_out/vq_leg.log)"
 done
-B="python bench.py --steps 50 --warmup 10 --no-sampler --no-roofline --no-config0 --no-cpu-baseline"
+B="python bench.py --full --steps 50 --warmup 10 --no-sampler --no-roofline --no-config0 --no-cpu-baseline"
 for i in 1 2 3; do
   for rg in 0 4; do
     TVQ_VQ_RG=$rg timeout -k 10 300 $B > gpurun_out/ab_vq.log 2>&1 || { tail -20 gpurun_out/ab_vq.log; exit 1; }

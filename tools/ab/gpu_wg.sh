@@ -14,7 +14,7 @@ done
 timeout -k 10 400 python -u -m pytest tests/test_graph.py tests/test_stage2.py tests/test_stage2_golden.py tests/test_stage1.py tests/test_dp_gpu.py -x -q -m gpu \
   --timeout 120 --timeout-method thread > gpurun_out/wg_step_tests.log 2>&1 || { tail -30 gpurun_out/wg_step_tests.log; exit 1; }
 tail -2 gpurun_out/wg_step_tests.log
-STEPARGS="--no-sampler --no-roofline --no-config0 --no-cpu-baseline"
+STEPARGS="--full --no-sampler --no-roofline --no-config0 --no-cpu-baseline"
 for v in 1 0; do
   TVQ_WGRAD_GROUP=$v timeout -k 10 300 python bench.py --steps 30 --warmup 5 $STEPARGS > gpurun_out/bench_step_wg$v.log 2>&1 || { tail -20 gpurun_out/bench_step_wg$v.log; exit 1; }
   echo "group=$v $(grep -o '"ms_per_step": [0-9.]*' gpurun_out/bench_step_wg$v.log)"

@@ -17,7 +17,7 @@ for v in new old; do
   echo "$v $(cat gpurun_out/r4b_leg_$v.json | grep -o '"avg_launch_us": [0-9.]*')"
   TVQ_HIP_LIB=$L timeout -s KILL 90 rocprofv3 --pmc SQ_BUSY_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_MFMA SQ_WAVES SQ_LDS_BANK_CONFLICT SQ_INSTS_LDS SQ_WAIT_ANY SQ_WAVE_CYCLES --output-format csv -d gpurun_out/r4b_sq_$v -o roof -- python tools/roofline_only.py rbbwd > gpurun_out/r4b_sq_$v.log 2>&1 || exit 1
 done
-B="python bench.py --steps 50 --warmup 10 --no-sampler --no-roofline --no-config0 --no-cpu-baseline"
+B="python bench.py --full --steps 50 --warmup 10 --no-sampler --no-roofline --no-config0 --no-cpu-baseline"
 for i in 1 2 3; do
   timeout -k 10 300 $B > gpurun_out/r4b_ab_new_$i.log 2>&1 || { tail -20 gpurun_out/r4b_ab_new_$i.log; exit 1; }
   echo "new $i $(grep -o '"ms_per_step": [0-9.]*' gpurun_out/r4b_ab_new_$i.log)"

@@ -23,7 +23,7 @@ done
 timeout -k 10 200 python tools/aten_sources.py > gpurun_out/r4c_aten_step.txt 2>&1 || { tail -20 gpurun_out/r4c_aten_step.txt; exit 1; }
 timeout -k 10 200 python tools/aten_sources.py sampler > gpurun_out/r4c_aten_sampler.txt 2>&1 || { tail -20 gpurun_out/r4c_aten_sampler.txt; exit 1; }
 echo aten-step; cat gpurun_out/r4c_aten_step.txt; echo aten-sampler; cat gpurun_out/r4c_aten_sampler.txt
-B="python bench.py --steps 50 --warmup 10 --no-sampler --no-roofline --no-config0 --no-cpu-baseline"
+B="python bench.py --full --steps 50 --warmup 10 --no-sampler --no-roofline --no-config0 --no-cpu-baseline"
 for i in 1 2 3; do
   for v in new rbold gbold; do
     L=$NEW; [ $v = rbold ] && L=$RBOLD; [ $v = gbold ] && L=$GBOLD

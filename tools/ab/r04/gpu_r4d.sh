@@ -9,7 +9,7 @@ timeout -k 10 900 python -u -m pytest tests -x -q -m gpu --timeout 240 --timeout
 tail -2 gpurun_out/r4d_tests.log
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > gpurun_out/r4d_smoke.log 2>&1 || { tail -20 gpurun_out/r4d_smoke.log; exit 1; }
 tail -3 gpurun_out/r4d_smoke.log
-STEPARGS="--no-sampler --no-roofline --no-config0 --no-cpu-baseline"
+STEPARGS="--full --no-sampler --no-roofline --no-config0 --no-cpu-baseline"
 rm -rf gpurun_out/r4d_prof
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/r4d_prof -o step -- python bench.py --steps 5 --warmup 2 $STEPARGS > gpurun_out/r4d_prof.log 2>&1 || { tail -20 gpurun_out/r4d_prof.log; exit 1; }
 T=$(find gpurun_out/r4d_prof -name "*kernel_trace.csv" | head -1)

@@ -7,7 +7,7 @@ cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 timeout -k 10 600 python -u -m pytest tests/test_tied_ce.py tests/test_groupby.py tests/test_stage2_golden.py tests/test_stage2.py tests/test_fullsize_parity.py tests/test_vq.py tests/test_dp_gpu.py -x -q -m gpu \
   --timeout 240 --timeout-method thread > gpurun_out/r4e_tests.log 2>&1 || { tail -40 gpurun_out/r4e_tests.log; exit 1; }
 tail -2 gpurun_out/r4e_tests.log
-STEPARGS="--no-sampler --no-roofline --no-config0 --no-cpu-baseline"
+STEPARGS="--full --no-sampler --no-roofline --no-config0 --no-cpu-baseline"
 B="python bench.py --steps 100 --warmup 10 $STEPARGS"
 for i in 1 2 3; do
   timeout -k 10 300 $B > gpurun_out/r4e_ab_new_$i.log 2>&1 || { tail -20 gpurun_out/r4e_ab_new_$i.log; exit 1; }

@@ -11,7 +11,7 @@ for i in 1 2; do
   timeout -k 10 300 python tools/sampler_graph_prof.py 20 > gpurun_out/r4k_samp_$i.log 2>&1 || { tail -20 gpurun_out/r4k_samp_$i.log; exit 1; }
   echo "sampler $(tail -1 gpurun_out/r4k_samp_$i.log)"
 done
-STEPARGS="--no-sampler --no-roofline --no-config0 --no-cpu-baseline"
+STEPARGS="--full --no-sampler --no-roofline --no-config0 --no-cpu-baseline"
 for i in 1 2 3; do
   timeout -k 10 300 python bench.py --steps 100 --warmup 10 $STEPARGS > gpurun_out/r4k_step_$i.log 2>&1 || { tail -20 gpurun_out/r4k_step_$i.log; exit 1; }
   echo "step $(grep -o '"ms_per_step": [0-9.]*' gpurun_out/r4k_step_$i.log)"

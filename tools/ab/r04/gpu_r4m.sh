@@ -7,7 +7,7 @@ cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 timeout -k 10 400 python -u -m pytest tests/test_fused_ff.py tests/test_stage2.py tests/test_stage2_golden.py tests/test_fullsize_parity.py tests/test_graph.py tests/test_dp_gpu.py -x -q -m gpu \
   --timeout 200 --timeout-method thread > gpurun_out/r4m_t1.log 2>&1 || { tail -60 gpurun_out/r4m_t1.log; exit 1; }
 tail -2 gpurun_out/r4m_t1.log
-STEPARGS="--no-sampler --no-roofline --no-config0 --no-cpu-baseline"
+STEPARGS="--full --no-sampler --no-roofline --no-config0 --no-cpu-baseline"
 for i in 1 2 3; do
   timeout -k 10 300 python bench.py --steps 100 --warmup 10 $STEPARGS > gpurun_out/r4m_new_$i.log 2>&1 || { tail -20 gpurun_out/r4m_new_$i.log; exit 1; }
   echo "fused $(grep -o '"ms_per_step": [0-9.]*' gpurun_out/r4m_new_$i.log)"

@@ -5,7 +5,7 @@ mkdir -p gpurun_out
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 timeout -k 10 900 python -u -m pytest -x -q --timeout 200 --timeout-method thread -m gpu tests/test_conv_bn_eval.py tests/test_stage2_golden.py tests/test_stage2.py tests/test_graph.py tests/test_sampler_full.py > gpurun_out/r4r_tests.log 2>&1 || { tail -40 gpurun_out/r4r_tests.log; exit 1; }
 tail -1 gpurun_out/r4r_tests.log
-STEPARGS="--no-sampler --no-roofline --no-config0 --no-cpu-baseline"
+STEPARGS="--full --no-sampler --no-roofline --no-config0 --no-cpu-baseline"
 for i in 1 2; do
 for F in 1 0; do
 TVQ_FUSED_BN_EVAL=$F timeout -k 10 300 python bench.py --steps 30 --warmup 5 $STEPARGS > gpurun_out/r4r_bench.log 2>&1 || { tail -20 gpurun_out/r4r_bench.log; exit 1; }

@@ -5,7 +5,7 @@ mkdir -p gpurun_out
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 timeout -k 10 900 python -u -m pytest -x -q --timeout 240 --timeout-method thread -m gpu tests/test_conv_halo_cc.py tests/test_ops_gpu.py tests/test_stage1.py tests/test_fullsize_parity.py tests/test_conv_bn_eval.py tests/test_sampler_full.py > gpurun_out/r4t_tests.log 2>&1 || { tail -40 gpurun_out/r4t_tests.log; exit 1; }
 tail -1 gpurun_out/r4t_tests.log
-STEPARGS="--no-sampler --no-roofline --no-config0 --no-cpu-baseline"
+STEPARGS="--full --no-sampler --no-roofline --no-config0 --no-cpu-baseline"
 for i in 1 2; do
 for H in 1 0; do
 TVQ_CONV_HCC=$H timeout -k 10 300 python bench.py --steps 30 --warmup 5 $STEPARGS > gpurun_out/r4t_bench.log 2>&1 || { tail -20 gpurun_out/r4t_bench.log; exit 1; }

@@ -8,7 +8,7 @@ timeout -k 10 500 python -u -m pytest ${R5T:-tests/test_resblock.py tests/test_s
   -x -q --timeout 200 --timeout-method thread \
   > gpurun_out/norm_tests.log 2>&1 || { tail -30 gpurun_out/norm_tests.log; exit 1; }
 tail -2 gpurun_out/norm_tests.log
-A="--steps 10 --warmup 3 --no-roofline --no-config0 --no-cpu-baseline --no-stage-legs"
+A="--full --steps 10 --warmup 3 --no-roofline --no-config0 --no-cpu-baseline --no-stage-legs"
 for rep in 1 2; do
   for lib in default $ALT; do
     if [ "$lib" = default ]; then E=""; else E="TVQ_HIP_LIB=$lib"; fi

@@ -2,15 +2,16 @@
 # A/B of a library build (lib_ab/, base) against the in-tree build: per-kernel time of the
 # step's named kernel under rocprofv3 (5 graph-replayed steps each), then the joint step alternated
 set -o pipefail
-mkdir -p gpurun_out/rrab
+OUT=${OUT:-bench_out}
+mkdir -p $OUT/rrab
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 K=${AB_KERNEL:-reduce_rows_batch4}
 STEPARGS="--no-sampler --no-roofline --no-config0 --no-cpu-baseline --no-stage-legs"
 for n in base new; do
   if [ $n = base ]; then export TVQ_HIP_LIB=$GRAFT_REPO_ROOT/lib_ab/libtvq_hip.so; else unset TVQ_HIP_LIB; fi
-  rm -rf gpurun_out/rrab/p$n
-  timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d gpurun_out/rrab/p$n -o p -- python bench.py --steps 5 --warmup 2 $STEPARGS > gpurun_out/rrab/p$n.log 2>&1 || { tail -20 gpurun_out/rrab/p$n.log; exit 1; }
-  T=$(find gpurun_out/rrab/p$n -name "*kernel_trace.csv" | head -1)
+  rm -rf $OUT/rrab/p$n
+  timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d $OUT/rrab/p$n -o p -- python bench.py --steps 5 --warmup 2 $STEPARGS > $OUT/rrab/p$n.log 2>&1 || { tail -20 $OUT/rrab/p$n.log; exit 1; }
+  T=$(find $OUT/rrab/p$n -name "*kernel_trace.csv" | head -1)
   python - "$T" "$K" $n <<'PY'
 import csv, sys, collections
 d = collections.defaultdict(list)
@@ -28,7 +29,7 @@ show() { python -c "import json;d=json.loads(open('$1').read().strip().splitline
 for rep in 1 2; do
   for n in base new; do
     if [ $n = base ]; then export TVQ_HIP_LIB=$GRAFT_REPO_ROOT/lib_ab/libtvq_hip.so; else unset TVQ_HIP_LIB; fi
-    timeout -k 10 300 python bench.py --steps 40 --warmup 5 --no-roofline --no-config0 --no-cpu-baseline --no-sampler > gpurun_out/rrab/b$n.log 2>&1 || { tail -5 gpurun_out/rrab/b$n.log; exit 1; }
-    echo "$n $(show gpurun_out/rrab/b$n.log)"
+    timeout -k 10 300 python bench.py --full --steps 40 --warmup 5 --no-roofline --no-config0 --no-cpu-baseline --no-sampler > $OUT/rrab/b$n.log 2>&1 || { tail -5 $OUT/rrab/b$n.log; exit 1; }
+    echo "$n $(show $OUT/rrab/b$n.log)"
   done
 done

@@ -4,7 +4,7 @@
 set -o pipefail
 mkdir -p gpurun_out
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
-B="python bench.py --steps 50 --warmup 10 --no-sampler --no-roofline --no-config0 --no-cpu-baseline"
+B="python bench.py --full --steps 50 --warmup 10 --no-sampler --no-roofline --no-config0 --no-cpu-baseline"
 run() { # name env...
   local n=$1; shift
   env "$@" timeout -k 10 300 $B > gpurun_out/att_$n.log 2>&1 || { tail -20 gpurun_out/att_$n.log; exit 1; }

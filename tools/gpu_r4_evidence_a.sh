@@ -5,7 +5,7 @@
 set -o pipefail
 mkdir -p gpurun_out/r4ev
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
-STEPARGS="--no-sampler --no-roofline --no-config0 --no-cpu-baseline"
+STEPARGS="--full --no-sampler --no-roofline --no-config0 --no-cpu-baseline"
 rm -rf gpurun_out/r4ev/step
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/r4ev/step -o step -- python bench.py --steps 5 --warmup 2 $STEPARGS > gpurun_out/r4ev/step.log 2>&1 || { tail -20 gpurun_out/r4ev/step.log; exit 1; }
 T=$(find gpurun_out/r4ev/step -name "*kernel_trace.csv" | head -1)

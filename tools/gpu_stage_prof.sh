@@ -4,7 +4,7 @@
 set -o pipefail
 mkdir -p gpurun_out
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
-STEPARGS="--no-sampler --no-roofline --no-config0 --no-cpu-baseline"
+STEPARGS="--full --no-sampler --no-roofline --no-config0 --no-cpu-baseline"
 for part in stage2 LF HF; do
   rm -rf gpurun_out/prof_$part
   if [ $part = stage2 ]; then E="TVQ_BENCH_ONLY=stage2"; else E="TVQ_BENCH_ONLY=stage1 TVQ_BENCH_BANDS=$part"; fi

@@ -6,7 +6,7 @@ cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 timeout -k 10 300 python -u -m pytest tests/test_ops_gpu.py -x -q -m gpu -k "gemm or linear" \
   --timeout 120 --timeout-method thread > gpurun_out/gemm_tests.log 2>&1 || { tail -30 gpurun_out/gemm_tests.log; exit 1; }
 tail -2 gpurun_out/gemm_tests.log
-STEPARGS="--no-sampler --no-roofline --no-config0 --no-cpu-baseline"
+STEPARGS="--full --no-sampler --no-roofline --no-config0 --no-cpu-baseline"
 timeout -k 10 300 python bench.py --steps 30 --warmup 5 $STEPARGS > gpurun_out/bench_step.log 2>&1 || { tail -20 gpurun_out/bench_step.log; exit 1; }
 tail -1 gpurun_out/bench_step.log | cut -c1-400
 rm -rf gpurun_out/prof_step3
