@@ -2,6 +2,7 @@
 import torch
 
 from ._native import call, grad_sink, ptr, stream_ptr, value
+from .conv import PackCache, _Conv2d
 
 
 def _dims(x):
@@ -93,6 +94,42 @@ def _bn_snake_bwd(ctx, gy):
     return dx, dw, db, da, None, None, None, None, None
 
 
+class _Conv1x1Uncached(_Conv2d):
+    """conv2d whose weight is computed per call: it never enters an open PackCache scope
+    (forward or backward), as the folded weights of hip.upscale."""
+
+    @staticmethod
+    def forward(ctx, *args):
+        with PackCache.paused():
+            return _Conv2d.forward(ctx, *args)
+
+    @staticmethod
+    def backward(ctx, gy):
+        with PackCache.paused():
+            return _Conv2d.backward(ctx, gy)
+
+
+def _bn_eval_grad(x, bn, a):
+    """snake_a(BatchNorm_eval(x)) with autograd: a frozen BatchNorm (eval mode, running
+    statistics untouched) inside a graph that trains.  In eval mode the BatchNorm is the
+    per-channel affine map u = x * s + t, s = w / sqrt(running_var + eps), t = b -
+    running_mean * s: it runs as the 1x1 convolution with weight diag(s) and bias t (conv2d's
+    forward, dgrad and wgrad kernels), then Snake; autograd takes dw / db from the diagonal of
+    the weight gradient and from the bias gradient through the C-element expressions below.
+    Not a hot path (no step of the trainers freezes a BatchNorm)."""
+    C = x.shape[1]
+    s = torch.rsqrt(bn.running_var + bn.eps)
+    if bn.weight is not None:
+        s = bn.weight * s
+    t = -bn.running_mean * s
+    if bn.bias is not None:
+        t = bn.bias + t
+    x4 = x.reshape(x.shape[0], C, 1, -1) if x.dim() != 4 else x
+    u = _Conv1x1Uncached.apply(x4, torch.diag(s).view(C, C, 1, 1), t, 1, False, None, 0.0, 0)
+    u = u.view(x.shape)
+    return _Snake.apply(u, a) if a is not None else u
+
+
 def bn_snake(x, bn, a=None):
     """snake_a(BatchNorm(x)) with the module `bn`'s parameters/buffers; a: the Snake
     parameter ((1,C,1,1) or (C,)) or None."""
@@ -101,8 +138,9 @@ def bn_snake(x, bn, a=None):
             raise NotImplementedError("cumulative-average BatchNorm (momentum=None) is not on the path")
         return _BNSnakeTrain.apply(x, bn.weight, bn.bias, a, bn.running_mean, bn.running_var,
                                    bn.num_batches_tracked, bn.momentum, bn.eps)
-    if torch.is_grad_enabled() and (x.requires_grad or (bn.weight is not None and bn.weight.requires_grad)):
-        raise NotImplementedError("eval-mode BatchNorm backward is not on the TimeVQVAE path")
+    if torch.is_grad_enabled() and (x.requires_grad or any(
+            p is not None and p.requires_grad for p in (bn.weight, bn.bias, a))):
+        return _bn_eval_grad(x, bn, a)
     x = x.contiguous()
     B, C, HW = _dims(x)
     y = torch.empty_like(x)

@@ -241,9 +241,23 @@ class _FusedFF(torch.autograd.Function):
                 db2, None, None, None)
 
 
-def fused_ff_supported(x, w1, w2):
-    return (FUSED_FF and x.is_cuda and x.shape[-1] == 128 and tuple(w1.shape) == (128, 128)
-            and tuple(w2.shape) == (128, 128))
+def _param16(w):
+    """fp32 device parameter read in place with 16-byte loads.  A FusedAdamW flat buffer packs
+    parameters without padding, so check, don't assume."""
+    return (w.dtype == torch.float32 and w.is_cuda and w.is_contiguous() and
+            w.data_ptr() % 16 == 0)
+
+
+def fused_ff_supported(x, w1, w2, b1=None, b2=None):
+    """Whether the fused feed-forward branch (tvq_ffn_*) takes this layer: width 128 in and
+    out, fp32 device weights and biases on 16-byte boundaries (tvq_ffn_fwd rejects others);
+    the rest take the per-op path."""
+    if not (FUSED_FF and x.is_cuda and x.shape[-1] == 128 and tuple(w1.shape) == (128, 128)
+            and tuple(w2.shape) == (128, 128) and x.dtype == torch.float32):
+        return False
+    if x.is_contiguous() and x.data_ptr() % 16 != 0:  # read in place (others are copied)
+        return False
+    return all(_param16(w) for w in (w1, w2, b1, b2) if w is not None)
 
 
 def fused_ff(xn, r, w1, b1, w2, b2, gate, p, site):

@@ -30,7 +30,8 @@ from ..hip.linear import gemm, linear, weight_product
 from ..hip.norm import bn_snake
 from ..hip.xf import (attn_branch, attn_branch_supported, batch_colsum, drop_first_token,
                       embed_assemble, embedding, fused_ff, fused_ff_supported, gelu,
-                      layer_norm, linear_act, prior_lf_eval, prior_lf_eval_sample,
+                      layer_norm, linear_act, masked_cross_entropy, prior_lf_eval,
+                      prior_lf_eval_sample,
                       prior_lf_eval_supported, prior_lf_eval_workspace, qkv_attention, rmsnorm, rmsnorm_res,
                       upsample_nearest_t)
 from ..hip._native import call, grad_sink, ptr, stream_ptr, value
@@ -100,7 +101,7 @@ class FeedForward(nn.Module):
         lin1 = self.ff[0][0]
         p = self.ff[1].p if self.training else 0.0
         lin2 = self.ff[2]
-        if fused_ff_supported(x, lin1.weight, lin2.weight):
+        if fused_ff_supported(x, lin1.weight, lin2.weight, lin1.bias, lin2.bias):
             # the whole branch + residual in one launch each way (hip.xf.fused_ff)
             return fused_ff(x, residual, lin1.weight, lin1.bias, lin2.weight, lin2.bias, gate, p,
                             self._site)
@@ -253,9 +254,11 @@ class _TiedLogits(torch.autograd.Function):
     @staticmethod
     def forward(ctx, h, W, bias, K):
         B, n, D = h.shape
+        rows = _bias_rows(bias, n, K)
+        bias = bias if bias.stride(1) == 1 else bias.contiguous()
         h2 = h.reshape(B * n, D).contiguous()
         M = B * n
-        out = gemm(h2, D, 1, W, 1, D, M, K, D, R=bias, ldr=bias.shape[1], rmod=n)
+        out = gemm(h2, D, 1, W, 1, D, M, K, D, R=bias, ldr=bias.stride(0), rmod=rows)
         ctx.save_for_backward(h2, W)
         ctx.W, ctx.bias = W, bias
         ctx.cfg = (B, n, D, K, tuple(bias.shape))
@@ -282,25 +285,51 @@ class _TiedLogits(torch.autograd.Function):
         if ctx.needs_input_grad[2]:
             # sum over the batch into the (n, K+1) table's first K columns, in order
             sink = grad_sink(ctx.bias)
+            g3 = g2.reshape(-1, bshape[0], K)  # a one-row bias sums over the tokens too
             if sink is not None:
                 with streams.offload(g2):
-                    batch_colsum(g2.reshape(B, n, K), sink, bshape[1], True)
+                    batch_colsum(g3, sink, bshape[1], True)
             else:
                 dbias = torch.zeros(bshape, device=g.device)
-                batch_colsum(g2.reshape(B, n, K), dbias, bshape[1], False)
+                batch_colsum(g3, dbias, bshape[1], False)
         return dh, dW, dbias, None
+
+
+def _bias_rows(bias, n, K):
+    """The row count of the tied logits' bias against n tokens: n rows (one per position, the
+    priors' own table) or one row broadcast over the positions; anything else is the shape
+    error torch's broadcast of `logits + bias` raises, never a wrapped row index."""
+    if bias.dim() != 2 or bias.shape[0] not in (1, n) or bias.shape[1] < K:
+        raise ValueError(f"tied logits: bias {tuple(bias.shape)} does not broadcast against "
+                         f"({n}, {K}) logits")
+    return bias.shape[0]
+
+
+def _reads_aligned(t):
+    """The kernels read `t` (after .contiguous()) with 16-byte loads: a contiguous tensor as
+    it lies, e.g. a view into FusedAdamW's flat buffer, which packs without padding; any
+    other is copied into a fresh allocation first."""
+    return t.dtype == torch.float32 and (not t.is_contiguous() or t.data_ptr() % 16 == 0)
 
 
 TIED_CE_FUSED = True  # False (tests): logits GEMM + masked CE forward / backward launches
 
 
-def tied_ce_supported(h, W, K):
+def tied_ce_supported(h, W, K, bias=None):
     """Fused for both priors: at the LF prior's 6144 tokens the kernel is slower alone (96
     blocks, ~100 us against ~70 us for the unfused launches) but the joint step is 0.02 ms
     faster with it (fewer launches and no logits round trip; tools/step_ab.py, same box:
     3.915-3.928 vs 3.940-3.947 ms)."""
-    return (h.is_cuda and h.dim() == 3 and h.shape[-1] == 128 and W.shape[1] == 128
-            and K in (64, 128, 256, 512) and W.shape[0] >= K)
+    if not (h.is_cuda and h.dim() == 3 and h.shape[-1] == 128 and W.shape[1] == 128
+            and K in (64, 128, 256, 512) and W.shape[0] >= K):
+        return False
+    # tvq_tied_logits_ce takes bias row m % rows and rejects unaligned h / W: only the
+    # per-position table and 16-byte aligned operands; the rest go the unfused way
+    if bias is not None and not (bias.dim() == 2 and bias.shape[0] == h.shape[1]
+                                 and bias.shape[1] >= K and bias.stride(1) == 1
+                                 and bias.dtype == torch.float32):
+        return False
+    return _reads_aligned(h) and _reads_aligned(W)
 
 
 class _TiedLogitsCE(torch.autograd.Function):
@@ -363,7 +392,11 @@ class _TiedLogitsCE(torch.autograd.Function):
 
 def tied_logits_ce(h, W, bias, K, target, keep, gscale):
     """The prior's masked CE loss from its head output h (B, n, 128) in one fused pass; the
-    backward is meant to start here with root gradient `gscale` (see _TiedLogitsCE)."""
+    backward is meant to start here with root gradient `gscale` (see _TiedLogitsCE).  What
+    tied_ce_supported declines (a broadcast bias row, unaligned operands, another width) runs
+    as the logits GEMM and the masked cross-entropy; a bias that does not broadcast raises."""
+    if not tied_ce_supported(h, W, K, bias):
+        return masked_cross_entropy(_TiedLogits.apply(h, W, bias, int(K)), target, keep)
     return _TiedLogitsCE.apply(h, W, bias, int(K), target, keep, gscale)
 
 

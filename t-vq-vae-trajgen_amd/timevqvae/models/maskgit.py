@@ -201,7 +201,7 @@ class MaskGIT(nn.Module):
         if one is not None and bt.TIED_CE_FUSED and (y is None or self.cfg_scale == 1.0):
             h = tf._embed_hf(*s_in, y) if tf.kind == "hf" else tf._embed_lf(s_in[0], y)
             W = tf.tok_emb_h.weight if tf.kind == "hf" else tf.tok_emb_l.weight
-            if bt.tied_ce_supported(h, W, tf.codebook_size):
+            if bt.tied_ce_supported(h, W, tf.codebook_size, tf.bias):
                 return bt.tied_logits_ce(h, W, tf.bias, tf.codebook_size, target, keep, one)
             logits = bt._TiedLogits.apply(h, W, tf.bias, tf.codebook_size)
             return masked_cross_entropy(logits, target, keep)

@@ -194,8 +194,9 @@ class VQVAEEncBlock(nn.Module):
         if bn_eval_fusable(x, b[1], b[0].weight, b[0].bias, b[2].a):
             return conv2d_bn_eval(x, b[0].weight, b[0].bias, b[1], _a(b[2]), stride_w=2,
                                   replicate=True)
-        if self.training and BN_STATS_IN_CONV and bnstats_blocks(x, b[0].weight, 2, False):
-            # the BN statistics in the conv's epilogue, finished by the apply launch
+        if b[1].training and BN_STATS_IN_CONV and bnstats_blocks(x, b[0].weight, 2, False):
+            # the BN statistics in the conv's epilogue, finished by the apply launch; by the
+            # BatchNorm's own mode, as bn_snake decides (a frozen BN keeps its statistics)
             h, part = conv2d_bnstats(x, b[0].weight, b[0].bias, stride_w=2, replicate=True)
             return bn_snake_part(h, part, b[1], _a(b[2]))
         h = conv2d(x, b[0].weight, b[0].bias, stride_w=2, replicate=True)
@@ -217,7 +218,7 @@ class VQVAEDecBlock(nn.Module):
             raise NotImplementedError("DecBlock dropout>0 is not on the path")
         if bn_eval_fusable(x, b[1], b[0].weight, b[0].bias, b[2].a):
             return conv_transpose2d_bn_eval(x, b[0].weight, b[0].bias, b[1], _a(b[2]))
-        if self.training and BN_STATS_IN_CONV and bnstats_blocks(x, b[0].weight, 2, True):
+        if b[1].training and BN_STATS_IN_CONV and bnstats_blocks(x, b[0].weight, 2, True):
             h, part = conv_transpose2d_bnstats(x, b[0].weight, b[0].bias, stride_w=2)
             return bn_snake_part(h, part, b[1], _a(b[2]))
         h = conv_transpose2d(x, b[0].weight, b[0].bias, stride_w=2)
