@@ -152,6 +152,41 @@ int tvq_vq_backward(const float* x, const float* quant, const float* dquant,
                     const float* gcommit, int64_t n, int64_t numel, float* dx,
                     tvq_stream_t stream);
 
+/* ---- codebook health: k-means init and dead-code expiry (csrc/tvq_vq_init.hip) ---- */
+
+/* sample_vectors' row choice (vq.py:67-75) on the device: sel[k], k < K, int32 row indices
+ * in [0, M).  M >= K: the first K values of a keyed pseudo-random permutation of [0, M)
+ * (distinct, the counterpart of randperm(M)[:K], vq.py:71); M < K: K i.i.d. uniform indices
+ * (randint, vq.py:73).  Keyed on (*seed_ptr, offset): the device seed of hip/rng.py, read by
+ * the kernel, so a captured graph redraws on every replay. */
+int tvq_vq_draw_rows(int64_t M, int64_t K, const int64_t* seed_ptr, uint64_t offset,
+                     int32_t* sel, tvq_stream_t stream);
+
+/* expire_codes_ / replace (vq.py:181-195) without the host read of vq.py:192: for every k
+ * with cluster_size[k] < threshold, embed[k,:] = x[row sel[k],:] (row m = x[m / N, m % N, :],
+ * element strides sB,sN,sD as tvq_vq_assign).  Only embed is written (embed_avg and
+ * cluster_size keep their values, as in the reference); no expired code, no write.
+ * sel == NULL: the kernel draws row k itself, exactly tvq_vq_draw_rows(M, K, seed_ptr,
+ * offset)[k]; otherwise sel (K int32, injected by tests) is used and seed_ptr may be NULL.
+ * n_expired (nullable): receives the number of expired codes. */
+int tvq_vq_expire(const float* x, int64_t B, int64_t N, int64_t D, int64_t sB, int64_t sN,
+                  int64_t sD, const int32_t* sel, const int64_t* seed_ptr, uint64_t offset,
+                  const float* cluster_size, float threshold, int64_t K, float* embed,
+                  int32_t* n_expired, tvq_stream_t stream);
+
+/* kmeans (vq.py:78-106, Euclidean): means = x[sel] (vq.py:81), then `iters` >= 1 times
+ *   buckets = argmin_k |x - mean_k|^2 (first index on ties; evaluated in the expansion form
+ *             of tvq_vq_assign, vq.py:87-92), bins = bincount(buckets) (vq.py:93),
+ *   means   = where(bins == 0, means, scatter_add(x by bucket) / max(bins, 1)) (vq.py:94-104).
+ * Outputs means (K,D) and bins (K, float): the counts of the last assignment (vq.py:106).
+ * The whole fit is enqueued on `stream` with no host synchronisation; deterministic (no float
+ * atomics).  D must be one of 32, 64, 128.  workspace: tvq_vq_kmeans_workspace(M, K, D)
+ * int32s, M = B*N. */
+int64_t tvq_vq_kmeans_workspace(int64_t M, int64_t K, int64_t D);
+int tvq_vq_kmeans(const float* x, int64_t B, int64_t N, int64_t D, int64_t sB, int64_t sN,
+                  int64_t sD, const int32_t* sel, int64_t K, int64_t iters, float* means,
+                  float* bins, int32_t* workspace, tvq_stream_t stream);
+
 
 /* ------------------------------------------------------------ STFT / iSTFT
  * time_to_timefreq + zero_pad_{high,low}_freq(copy=True) + the stage1 targets

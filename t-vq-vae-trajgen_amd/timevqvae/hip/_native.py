@@ -98,6 +98,10 @@ sig("tvq_vq_assign_svq", P, I64, I64, I64, I64, I64, I64, P, P, I64, I32, F32, P
     P, P)
 sig("tvq_vq_assign_rows", P, I64, I64, I64, I64, I64, I64, P, P, I64, I32, F32, P, P, U64, P, P, P,
     P, P, P)
+sig("tvq_vq_draw_rows", I64, I64, P, U64, P, P)
+sig("tvq_vq_expire", P, I64, I64, I64, I64, I64, I64, P, P, U64, P, F32, I64, P, P, P)
+sig("tvq_vq_kmeans_workspace", I64, I64, I64, restype=I64)
+sig("tvq_vq_kmeans", P, I64, I64, I64, I64, I64, I64, P, I64, I64, P, P, P, P)
 # --- STFT / iSTFT ------------------------------------------------------------
 sig("tvq_stft_encode", P, I64, I64, I64, P, P, P, P, P, P)
 sig("tvq_istft_decode", P, I64, I64, I64, I64, I64, P, P)

@@ -8,6 +8,20 @@ keep the reference constructor signature, buffer names
 distance + argmin, deterministic EMA statistics, straight-through gradient.
 The M x K one-hot of the reference (vq.py:223, 233) is never materialised;
 `embed_onehot` is therefore not kept (no caller reads it).
+
+The two codebook-health options of the reference are on the same path:
+`kmeans_init=True` (vq.py:170-179: the first forward, in either mode, fits the codebook to
+its own batch by k-means, hip.vq.kmeans_init) and `threshold_ema_dead_code > 0`
+(vq.py:187-195, 243: a training forward ends by re-seeding every code whose EMA cluster size
+fell below the threshold from a random token row of the batch, hip.vq.expire).  The k-means
+fit is a one-off eager step: a codebook that is still uninitialised when a stream is being
+captured raises (StepGraph's eager warm-up steps run the fit before the capture).  The
+expiry is one unconditional launch with no host read (vq.py:192's `torch.any` is dropped:
+no expired code, no write) and draws its rows from the device seed, so it is captured with
+the step and redraws on every replay.  Both options are refused under sync_codebook with
+more than one rank: the reference lets every rank fit / re-seed from its own shard, after
+which the replicas' codebooks differ.  `learnable_codebook` and `emb_dropout` stay off the
+path.
 """
 from typing import Union
 
@@ -15,6 +29,7 @@ import torch
 import torch.distributed as distributed
 from torch import nn
 
+from ..hip import vq as hip_vq
 from ..hip.vq import vq_codebook_pass, vq_train
 
 
@@ -41,18 +56,19 @@ def laplace_smoothing(x, n_categories, eps=1e-5):
 
 
 class EuclideanCodebook(nn.Module):
-    """vq.py:124-251 (kmeans_init=False, learnable_codebook=False on the hot path)."""
+    """vq.py:124-251 (learnable_codebook=False, emb_dropout=0)."""
 
     def __init__(self, dim, codebook_size, kmeans_init=False, kmeans_iters=10, decay=0.8,
                  eps=1e-5, threshold_ema_dead_code=2, use_ddp=False, learnable_codebook=False,
                  sample_codebook_temp=0, emb_dropout=0.0):
         super().__init__()
-        if kmeans_init or learnable_codebook or emb_dropout:
+        if learnable_codebook or emb_dropout:
             raise NotImplementedError(
-                "kmeans_init / learnable_codebook / emb_dropout are not on the TimeVQVAE path "
+                "learnable_codebook / emb_dropout are not on the TimeVQVAE path "
                 "(configs never enable them)")
         self.decay = decay
-        embed = torch.randn(codebook_size, dim)
+        init_fn = torch.randn if not kmeans_init else torch.zeros  # vq.py:145-146
+        embed = init_fn(codebook_size, dim)
         self.codebook_size = codebook_size
         self.kmeans_iters = kmeans_iters
         self.eps = eps
@@ -69,6 +85,74 @@ class EuclideanCodebook(nn.Module):
         self.embed_onehot = None
         self.perplexity = None
         self.counts = None  # int32 (K,) per-code counts of the last pass (replaces embed_onehot)
+        # host mirror of the `initted` buffer (no forward reads the device buffer): set here,
+        # refreshed by load_state_dict, set by init_embed_
+        self._initted = not kmeans_init
+        self.expire_sel = None  # tests: int32 (K,) row choice of the next expiries
+
+    def _load_from_state_dict(self, state_dict, prefix, *args, **kwargs):
+        super()._load_from_state_dict(state_dict, prefix, *args, **kwargs)
+        t = state_dict.get(prefix + "initted")
+        if t is not None:
+            self._initted = bool(t.reshape(-1)[0].item() != 0)
+
+    def _refuse_multi_rank(self):
+        """kmeans_init / dead-code expiry under sync_codebook with more than one rank: the
+        reference fits and re-seeds from each rank's own shard, so the replicas diverge."""
+        if not self.use_ddp or (self._initted and self.threshold_ema_dead_code <= 0):
+            return
+        if not (distributed.is_available() and distributed.is_initialized()
+                and distributed.get_world_size() > 1):
+            return
+        opt = "kmeans_init" if not self._initted else "threshold_ema_dead_code > 0"
+        raise NotImplementedError(
+            f"{opt} with sync_codebook on {distributed.get_world_size()} ranks is not "
+            "supported: each rank would fit / re-seed the codebook from its own shard and "
+            "the replicas would diverge")
+
+    @torch.no_grad()
+    def init_embed_(self, data, sel=None):
+        """vq.py:170-179: once, fit the codebook to `data` ((M,D) or (B,N,D) token rows) by
+        k-means and set embed, embed_avg, cluster_size and initted.  `sel` (int32 (K,))
+        injects the initial rows (tests); None draws them on the device.  A one-off eager
+        step: it raises while a stream is being captured (run a step eagerly first, as
+        StepGraph's warm-up does)."""
+        if self._initted:
+            return
+        if data.is_cuda and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError(
+                "kmeans_init: the codebook is not initialised yet and a stream is being "
+                "captured; the k-means fit is a one-off eager step, run one forward eagerly "
+                "before capturing (StepGraph's warm-up steps do)")
+        self._refuse_multi_rank()
+        embed, cluster_size = hip_vq.kmeans_init(data, self.codebook_size, self.kmeans_iters,
+                                                 sel=sel)
+        self.embed.copy_(embed)
+        self.embed_avg.copy_(embed)
+        self.cluster_size.copy_(cluster_size)
+        self.initted.fill_(1.0)
+        self._initted = True
+
+    @torch.no_grad()
+    def replace(self, samples, mask, sel=None):
+        """vq.py:181-185: embed[k] = a sampled row of `samples` wherever mask[k]."""
+        hip_vq.expire(samples, self.embed, (~mask).to(torch.float32), 0.5, sel=sel)
+
+    @torch.no_grad()
+    def expire_codes_(self, batch_samples, sel=None):
+        """vq.py:187-195, without the host read: codes with cluster_size below the threshold
+        take a sampled row of the batch; embed_avg and cluster_size keep their values."""
+        if self.threshold_ema_dead_code == 0:
+            return
+        hip_vq.expire(batch_samples, self.embed, self.cluster_size, self.threshold_ema_dead_code,
+                      sel=sel)
+
+    def _expire_threshold(self):
+        """The expiry threshold of a training pass (0: off)."""
+        if self.threshold_ema_dead_code > 0:
+            self._refuse_multi_rank()
+            return self.threshold_ema_dead_code
+        return 0
 
     def _sync(self):
         if self.use_ddp and distributed.is_available() and distributed.is_initialized():
@@ -79,14 +163,15 @@ class EuclideanCodebook(nn.Module):
     def forward(self, x, svq_temp: Union[float, None] = None):
         """Returns (quantize = E_old[idx], embed_ind); EMA update when training (vq.py:197-251).
         svq_temp > 0 samples idx ~ Categorical(softmax(dist / svq_temp)) (vq.py:216-222)."""
-        if self.threshold_ema_dead_code > 0 and self.training:
-            raise NotImplementedError("threshold_ema_dead_code > 0 is not on the TimeVQVAE path")
         shape = x.shape
         x3 = x.reshape(1, -1, shape[-1]) if x.dim() != 3 else x
+        if not self._initted:
+            self.init_embed_(x3)
         q, idx, _, perp, counts = vq_codebook_pass(
             x3, self.embed, self.cluster_size, self.embed_avg, straight_through=False,
             ema=self.training, decay=self.decay, eps=self.eps, sync=self._sync(),
-            svq_temp=svq_temp)
+            svq_temp=svq_temp, expire_threshold=self._expire_threshold() if self.training else 0,
+            expire_sel=self.expire_sel)
         self.perplexity = perp
         self.counts = counts
         return q.reshape(shape), idx.reshape(shape[:-1])
@@ -150,12 +235,13 @@ class VectorQuantize(nn.Module):
             x = x.flatten(2).transpose(1, 2)
         if not self.channel_last and not self.accept_image_fmap:
             x = x.transpose(1, 2)
+        if not cb._initted:  # vq.py:202: in either mode, before anything reads the codebook
+            cb.init_embed_(x)
         if self.training:
-            if cb.threshold_ema_dead_code > 0:
-                raise NotImplementedError("threshold_ema_dead_code > 0 is not on the path")
             quantize, embed_ind, commit, perp = vq_train(
                 x, cb.embed, cb.cluster_size, cb.embed_avg, ema=True, decay=cb.decay, eps=cb.eps,
-                sync=cb._sync(), svq_temp=svq_temp)
+                sync=cb._sync(), svq_temp=svq_temp, expire_threshold=cb._expire_threshold(),
+                expire_sel=cb.expire_sel)
             if self.commitment_weight > 0:
                 vq_loss["commit_loss"] = commit
                 # vq.py:364's [0.] + commit * w, shape (1,): at w == 1 that is commit itself
