@@ -2,7 +2,7 @@
 // models/fidelity_enhancer.py:96-455) on gfx950: the training-mode forward pieces that
 // differ from the eval kernels of tvq_fe.hip (GroupNorm+Snake with the Block's dropout
 // and saved statistics) and the backward of every Unet1D op that is not a convolution
-// (the convs run on the conv engine, tvq_conv.hip, as H = 1 images):
+// (the convs run on the conv engine, tvq_conv*.hip, as H = 1 images):
 //
 //   fe_ws_bwd               WeightStandardizedConv2d weight: dw = r (g - mean g - w^ mean(g w^))
 //   fe_gn_snake_train_fwd   GroupNorm -> Snake -> Dropout (+ ResnetBlock skip), per (b, g)
