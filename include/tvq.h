@@ -705,6 +705,19 @@ int tvq_prior_lf_eval_sample(const int64_t* s, int64_t B, int64_t n, int64_t s_s
                              int64_t mask_id, const float* gumbel, const int64_t* seed_ptr,
                              uint64_t offset, int64_t* sampled, float* selp, float* logits,
                              void* workspace, int64_t workspace_ready, tvq_stream_t stream);
+/* tvq_prior_lf_eval_sample with classifier-free guidance (MaskGIT.masked_prediction,
+ * maskgit.py:136-153): the draw is taken from logits_null + cfg_scale * (logits - logits_null),
+ * logits the prior's output for cls_idx (non-null here) and logits_null for the null class
+ * n_classes, both formed in the same launch (two waves per sequence) and neither written.
+ * logits (nullable) receives the MIXED logits.  Same weights order, same workspace (either
+ * entry may have packed it); cfg_scale must be finite. */
+int tvq_prior_lf_eval_sample_cfg(const int64_t* s, int64_t B, int64_t n, int64_t s_stride,
+                                 const int64_t* cls_idx, int64_t n_classes, int64_t width,
+                                 const float* const* weights, int64_t depth, int64_t K,
+                                 float ln_eps, float cfg_scale, int64_t mask_id,
+                                 const float* gumbel, const int64_t* seed_ptr, uint64_t offset,
+                                 int64_t* sampled, float* selp, float* logits, void* workspace,
+                                 int64_t workspace_ready, tvq_stream_t stream);
 
 /* ---------------------------------------------------------------- MaskGIT sampling
  * One iterative-decoding step of MaskGIT.first_pass / second_pass (maskgit.py:294-411):
@@ -722,7 +735,11 @@ int tvq_prior_lf_eval_sample(const int64_t* s, int64_t B, int64_t n, int64_t s_s
  * priors' tied output head, bidirectional_transformer.py:186-191; row m = b n + i) without
  * writing the logits: h (M, D), D 64 or 128; W (>= K, D); bias (n, ldb); h, W and the
  * workspace (tvq_tied_logits_sample_workspace(K, D, n) bytes) 16-byte aligned.
- * logits_out (M, K, nullable) receives the logits the draw used. */
+ * logits_out (M, K, nullable) receives the logits the draw used.
+ * tvq_tied_logits_sample_cfg: the same draw from the classifier-free-guidance mix
+ * l_null + cfg_scale * (l_cond - l_null), l_x = h_x W[:K]^T + bias (maskgit.py:136-153), the
+ * code table read once for both branches; h_cond, h_null (M, D) 16-byte aligned, cfg_scale
+ * finite, same workspace; logits_out receives the mixed logits. */
 int tvq_maskgit_sample(const float* logits, int64_t sb, int64_t sn, int64_t B, int64_t n,
                        int64_t K, const int64_t* s_in, int64_t mask_id, const float* gumbel,
                        const int64_t* seed_ptr, uint64_t offset, int64_t* sampled, float* selp,
@@ -733,6 +750,12 @@ int tvq_tied_logits_sample(const float* h, int64_t M, int64_t D, const float* W,
                            int64_t mask_id, const float* gumbel, const int64_t* seed_ptr,
                            uint64_t offset, int64_t* sampled, float* selp, float* logits_out,
                            void* workspace, tvq_stream_t stream);
+int tvq_tied_logits_sample_cfg(const float* h_cond, const float* h_null, int64_t M, int64_t D,
+                               const float* W, int64_t K, const float* bias, int64_t n,
+                               int64_t ldb, float cfg_scale, const int64_t* s_in, int64_t mask_id,
+                               const float* gumbel, const int64_t* seed_ptr, uint64_t offset,
+                               int64_t* sampled, float* selp, float* logits_out, void* workspace,
+                               tvq_stream_t stream);
 int tvq_maskgit_remask(const float* selp, int64_t B, int64_t n, int64_t k, float temperature,
                        const float* u_gumbel, const int64_t* seed_ptr, uint64_t offset,
                        const int64_t* sampled, int64_t mask_id, int64_t* s_out, uint8_t* masking,

@@ -388,15 +388,16 @@ __device__ __forceinline__ void pe_draw(PeStream& st, const floatx16 (&x)[4], Ra
   }
 }
 
-// one wave (64 threads) per sequence
-__global__ __launch_bounds__(64) void prior_lf_eval_kernel(PriorArgs a,
-                                                           const float4* __restrict__ wstream) {
-  const int l = threadIdx.x & 63, r32 = l & 31, h = l >> 5;
-  const bool seq_ok = true;
-  const int b = blockIdx.x;
+// The trunk of one wave: sequence b from the embedding to pred_head's LayerNorm.  On return
+// x holds h (the tied logits' input, token on the lane) and st stands at the first code tile.
+// null_cls: the null-class row n_classes instead of the sequence's class (the unconditional
+// branch of classifier-free guidance).
+__device__ __forceinline__ void pe_trunk(const PriorArgs& a, const float4* __restrict__ wstream,
+                                         int b, int l, bool null_cls, PeStream& st,
+                                         floatx16 (&x)[4]) {
+  const int r32 = l & 31, h = l >> 5;
   const int n = a.n, ntok = a.n + 1;  // tokens incl. cls (<= 32)
   const bool live = r32 < ntok;
-  PeStream st;
   st.src = wstream;
   st.ntiles = pe_ntiles(a.depth, a.K) - 4;  // project_in's tiles are folded into ftab
   st.depth = a.depth;
@@ -404,13 +405,12 @@ __global__ __launch_bounds__(64) void prior_lf_eval_kernel(PriorArgs a,
   pe_stream_begin(st);
   // ---- project_in(embedding) from the folded tables: the cls row, then token + position
   // rows (zeros on the padding lanes)
-  floatx16 x[4];
   {
     const int V = a.K + 1;
     const float* src;
     const float* pos = nullptr;
     if (r32 == 0) {
-      const int64_t c = a.cls ? a.cls[b] : (int64_t)a.n_classes;
+      const int64_t c = a.cls && !null_cls ? a.cls[b] : (int64_t)a.n_classes;
       src = a.ftab + (V + n + c) * PE_D;
     } else {
       const int i = live ? r32 - 1 : 0;
@@ -519,6 +519,18 @@ __global__ __launch_bounds__(64) void prior_lf_eval_kernel(PriorArgs a,
       for (int r = 0; r < 16; ++r) x[t][r] = pe_gelu(y[t][r]);
     pe_layernorm(x, a.ln_w, a.ln_b, a.ln_eps, h);
   }
+}
+
+// one wave (64 threads) per sequence
+__global__ __launch_bounds__(64) void prior_lf_eval_kernel(PriorArgs a,
+                                                           const float4* __restrict__ wstream) {
+  const int l = threadIdx.x & 63, r32 = l & 31, h = l >> 5;
+  const bool seq_ok = true;
+  const int b = blockIdx.x;
+  const int n = a.n;
+  PeStream st;
+  floatx16 x[4];
+  pe_trunk(a, wstream, b, l, false, st, x);
   const int ldb = a.K + 1;
   if (a.sampled) {
     // ---- tied logits token-on-the-lane (the code tile as the A operand: registers = codes
@@ -575,6 +587,166 @@ __global__ __launch_bounds__(64) void prior_lf_eval_kernel(PriorArgs a,
   }
 }
 
+// ---- classifier-free guidance (maskgit.py:136-153: logits_null + cfg_scale * (logits -
+// logits_null)) inside the draw launch.  One block of two waves per sequence: wave 0 runs the
+// trunk with the sequence's class row, wave 1 with the null-class row, from the same packed
+// stream; they meet once, when both head outputs h exist, through LDS.  Each wave then takes
+// a contiguous half of the code tiles, loads a tile once for two MFMA chains (B = h_cond,
+// B = h_null), mixes the two logits in fp32 and races on the mix with the counters of the
+// unguided draw; the waves' race states merge through LDS (race_merge is symmetric, ties to
+// the lowest code).  Neither branch's logits reach memory.
+
+// pe_gemm<true, NS> for two B operands on one pass over the tile
+template <int NS, class BC, class BN>
+__device__ __forceinline__ void pe_gemm2(PeStream& st, BC bc, BN bn, floatx16& accc,
+                                         floatx16& accn) {
+  constexpr int G = NS / 4;
+  static_assert(G >= PE_PRE, "tile shorter than the prefetch");
+  const int off = __builtin_amdgcn_readfirstlane((int)st.off);
+  const float4* cur = st.src + off;
+  float4 rest[G - PE_PRE > 0 ? G - PE_PRE : 1];
+#pragma unroll
+  for (int i = 0; i < G - PE_PRE; ++i) rest[i] = cur[(PE_PRE + i) * 64 + st.lane];
+  const int nidx = st.idx + 1;
+  const int noff = off + G * 64;
+  float4 nq[PE_PRE];
+  if (nidx < st.ntiles) {
+#pragma unroll
+    for (int i = 0; i < PE_PRE; ++i) nq[i] = st.src[noff + i * 64 + st.lane];
+  } else {
+#pragma unroll
+    for (int i = 0; i < PE_PRE; ++i) nq[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+  }
+#pragma unroll
+  for (int T4 = 0; T4 < G; ++T4) {
+    const float4 w4 = T4 < PE_PRE ? st.pre[T4] : rest[T4 - PE_PRE];
+    const float wv[4] = {w4.x, w4.y, w4.z, w4.w};
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      accc = pe_mfma(wv[e], bc(4 * T4 + e), accc);
+      accn = pe_mfma(wv[e], bn(4 * T4 + e), accn);
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < PE_PRE; ++i) st.pre[i] = nq[i];
+  st.off = noff;
+  st.idx = nidx;
+}
+
+// pe_draw on the guided mix, over the code tiles [c_lo, c_hi) (codes, multiples of 32)
+template <bool INJ, bool LOUT>
+__device__ __forceinline__ void pe_draw_cfg(PeStream& st, const float (&hc)[64],
+                                            const float (&hn)[64], float scale, RaceState& rs,
+                                            const float* __restrict__ brow,
+                                            const float* __restrict__ grow, uint32_t key,
+                                            uint32_t ctr0, float* __restrict__ lout,
+                                            bool store_ok, int c_lo, int c_hi, int K, int h) {
+  for (int c0 = c_lo; c0 < c_hi; c0 += 32) {
+    float bq[16];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) bq[r] = brow[min(c0 + race_crow(r, h), K - 1)];
+    floatx16 ac, an;
+    pe_zero(ac);
+    pe_zero(an);
+    pe_gemm2<64>(st, [&](int t) { return hc[t]; }, [&](int t) { return hn[t]; }, ac, an);
+    float v[16];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const float lc = bq[r] + ac[r], ln = bq[r] + an[r];
+      v[r] = ln + scale * (lc - ln);
+    }
+    if (LOUT) {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int code = c0 + race_crow(r, h);
+        if (store_ok && code < K) lout[code] = v[r];
+      }
+    }
+    race_tile<INJ>(rs, v, c0, h, K, grow, key, ctr0);
+  }
+}
+
+__global__ __launch_bounds__(128) void prior_lf_eval_cfg_kernel(
+    PriorArgs a, const float4* __restrict__ wstream, float cfg_scale) {
+  __shared__ float hx[2][64][64];  // [branch][MFMA step][lane]: h of both branches
+  __shared__ float mg_m[32], mg_best[32], mg_bl[32];
+  __shared__ double mg_s[32];
+  __shared__ int mg_bk[32];
+  const int l = threadIdx.x & 63, r32 = l & 31, h = l >> 5;
+  const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));  // 0: class, 1: null
+  const int b = blockIdx.x;
+  const int n = a.n;
+  PeStream st;
+  {
+    floatx16 x[4];
+    pe_trunk(a, wstream, b, l, w == 1, st, x);
+#pragma unroll
+    for (int t = 0; t < 64; ++t) hx[w][t][l] = x[t >> 4][t & 15];
+  }
+  __syncthreads();
+  float hc[64], hn[64];
+#pragma unroll
+  for (int t = 0; t < 64; ++t) {
+    hc[t] = hx[0][t][l];
+    hn[t] = hx[1][t][l];
+  }
+  // this wave's code tiles: wave 0 [0, ceil(Kt / 2)), wave 1 the rest (none when Kt == 1).
+  // The code tiles are 1024 float4 each and st stands at the first one.
+  const int Kt = (a.K + 31) / 32, half = (Kt + 1) / 2;
+  const int t_lo = w == 0 ? 0 : half, t_hi = w == 0 ? half : Kt;
+  if (w == 0) {
+    st.ntiles = st.idx + half;  // no prefetch into the other wave's tiles
+  } else {
+    st.idx += half;
+    st.off += (int64_t)1024 * half;
+    if (st.idx < st.ntiles) {
+#pragma unroll
+      for (int i = 0; i < PE_PRE; ++i) st.pre[i] = st.src[st.off + i * 64 + l];
+    }
+  }
+  const int ldb = a.K + 1;
+  const int tok = r32;
+  const bool tok_ok = tok >= 1 && tok <= n;
+  const int64_t t = (int64_t)b * n + (tok_ok ? tok - 1 : 0);
+  // as in prior_lf_eval_kernel: every lane reads valid (clamped) rows, only token lanes store
+  const float* brow = a.bias + (int64_t)(tok_ok ? tok - 1 : 0) * ldb;
+  const float* grow = a.gumbel ? a.gumbel + t * a.K : nullptr;
+  const uint32_t key = a.gumbel ? 0u : race_key(mix_seed(a.seed_ptr, a.offset));
+  float* lout = a.logits ? a.logits + t * a.K : nullptr;
+  RaceState rs;
+  race_init(rs);
+  const uint32_t ctr0 = (uint32_t)t * (uint32_t)a.K;
+  const int c_lo = 32 * t_lo, c_hi = 32 * t_hi;
+  if (!a.gumbel && !a.logits)
+    pe_draw_cfg<false, false>(st, hc, hn, cfg_scale, rs, brow, nullptr, key, ctr0, nullptr, tok_ok,
+                              c_lo, c_hi, a.K, h);
+  else if (!a.gumbel)
+    pe_draw_cfg<false, true>(st, hc, hn, cfg_scale, rs, brow, nullptr, key, ctr0, lout, tok_ok,
+                             c_lo, c_hi, a.K, h);
+  else if (!a.logits)
+    pe_draw_cfg<true, false>(st, hc, hn, cfg_scale, rs, brow, grow, key, ctr0, nullptr, tok_ok,
+                             c_lo, c_hi, a.K, h);
+  else
+    pe_draw_cfg<true, true>(st, hc, hn, cfg_scale, rs, brow, grow, key, ctr0, lout, tok_ok, c_lo,
+                            c_hi, a.K, h);
+  race_halves(rs);  // every lane: its token's state over this wave's codes
+  if (w == 1 && h == 0) {
+    mg_m[r32] = rs.m; mg_s[r32] = rs.s; mg_best[r32] = rs.best; mg_bl[r32] = rs.bl;
+    mg_bk[r32] = rs.bk;
+  }
+  __syncthreads();
+  if (w == 0 && h == 0 && tok_ok) {
+    race_merge(rs, mg_m[r32], mg_s[r32], mg_best[r32], mg_bl[r32], mg_bk[r32]);
+    int pick;
+    float p;
+    race_result(rs, pick, p);
+    const int64_t s0 = a.s[(int64_t)b * a.ss + tok - 1];
+    const bool known = s0 != a.mask_id;
+    a.sampled[t] = known ? s0 : (int64_t)pick;
+    a.selp[t] = known ? INFINITY : p;
+  }
+}
+
 }  // namespace tvq
 
 using namespace tvq;
@@ -593,7 +765,8 @@ static int prior_lf_eval_launch(PriorArgs& a, const int64_t* s, int64_t B, int64
                                 int64_t s_stride, const int64_t* cls_idx, int64_t n_classes,
                                 int64_t width, const float* const* weights, int64_t depth,
                                 int64_t K, float ln_eps, void* workspace, bool ready,
-                                tvq_stream_t stream, const char* name) {
+                                tvq_stream_t stream, const char* name,
+                                const float* cfg_scale = nullptr) {
   TVQ_CHECK_ARG(s && weights && B >= 1 && n >= 1 && n + 1 <= 32 && K >= 1 &&
                     width == PE_D && depth >= 1 && depth <= PE_MAXDEPTH && n_classes >= 0,
                 "tvq_prior_lf_eval: unsupported shape (width 128, n + 1 <= 32, depth <= 8)");
@@ -630,6 +803,12 @@ static int prior_lf_eval_launch(PriorArgs& a, const int64_t* s, int64_t B, int64
                        0, st, a);
     hipLaunchKernelGGL(prior_headfold_kernel, dim3(PE_D), dim3(PE_D), 0, st, a);
     hipLaunchKernelGGL(prior_pack_kernel, dim3((unsigned)(ntiles - 4)), dim3(256), 0, st, a, ws, 4);
+  }
+  if (cfg_scale) {  // the guided draw: two waves per sequence (class / null branch)
+    hipLaunchKernelGGL(prior_lf_eval_cfg_kernel, dim3((unsigned)B), dim3(128), 0, st, a,
+                       (const float4*)ws, *cfg_scale);
+    TVQ_PLAN("prior_lf_eval waves=2 (class, null)");
+    return launch_status(name);
   }
   hipLaunchKernelGGL(prior_lf_eval_kernel, dim3((unsigned)B), dim3(64), 0, st, a,
                      (const float4*)ws);
@@ -668,4 +847,30 @@ extern "C" int tvq_prior_lf_eval_sample(const int64_t* s, int64_t B, int64_t n, 
   return prior_lf_eval_launch(a, s, B, n, s_stride, cls_idx, n_classes, width, weights, depth, K,
                               ln_eps, workspace, workspace_ready != 0, stream,
                               "tvq_prior_lf_eval_sample");
+}
+
+extern "C" int tvq_prior_lf_eval_sample_cfg(const int64_t* s, int64_t B, int64_t n,
+                                            int64_t s_stride, const int64_t* cls_idx,
+                                            int64_t n_classes, int64_t width,
+                                            const float* const* weights, int64_t depth, int64_t K,
+                                            float ln_eps, float cfg_scale, int64_t mask_id,
+                                            const float* gumbel, const int64_t* seed_ptr,
+                                            uint64_t offset, int64_t* sampled, float* selp,
+                                            float* logits, void* workspace,
+                                            int64_t workspace_ready, tvq_stream_t stream) {
+  TVQ_CHECK_ARG(sampled && selp, "tvq_prior_lf_eval_sample_cfg: null outputs");
+  TVQ_CHECK_ARG(gumbel || seed_ptr, "tvq_prior_lf_eval_sample_cfg: need gumbel noise or a seed");
+  TVQ_CHECK_ARG(gumbel || B * n * K < (int64_t)1 << 32,
+                "tvq_prior_lf_eval_sample_cfg: B n K >= 2^32");
+  TVQ_CHECK_ARG(cls_idx, "tvq_prior_lf_eval_sample_cfg: guidance needs class indices");
+  TVQ_CHECK_ARG(cfg_scale - cfg_scale == 0.f, "tvq_prior_lf_eval_sample_cfg: cfg_scale must be finite");
+  PriorArgs a = {};
+  a.logits = logits;
+  a.mask_id = mask_id; a.gumbel = gumbel; a.seed_ptr = seed_ptr; a.offset = offset;
+  a.sampled = sampled; a.selp = selp;
+  TVQ_PLAN("prior_lf_eval_sample_cfg B=%lld n=%lld K=%lld", (long long)B, (long long)n,
+           (long long)K);
+  return prior_lf_eval_launch(a, s, B, n, s_stride, cls_idx, n_classes, width, weights, depth, K,
+                              ln_eps, workspace, workspace_ready != 0, stream,
+                              "tvq_prior_lf_eval_sample_cfg", &cfg_scale);
 }

@@ -2,7 +2,8 @@
 // "token on the lane" (v_mfma_f32_32x32x2_f32 with the code table as the A operand: lane
 // l holds token l & 31 and, in accumulator register r, code 32 c + crow(r, l >> 5) of
 // tile c).  Shared by the fused sampling epilogues (tied_logits_sample_kernel for the HF
-// prior, prior_lf_eval_kernel for the LF prior): the logits never reach HBM.
+// prior, prior_lf_eval_kernel for the LF prior, and their guided _cfg forms): the logits
+// never reach HBM.
 //
 // Per token: the race argmax_k l_k + g_k (torch.multinomial's n_sample = 1 algorithm,
 // tvq_common.h race_gumbel; ties to the lowest code), and p(pick) of the fp32 softmax --

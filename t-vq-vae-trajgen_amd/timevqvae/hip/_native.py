@@ -210,9 +210,13 @@ sig("tvq_attn_branch_bwd", P, P, I64, I64, I64, I64, P, F32, P, P, P, P, F32, P,
     P, P, I64, P, P)
 sig("tvq_prior_lf_eval_sample", P, I64, I64, I64, P, I64, I64, P, I64, I64, F32, I64, P, P, U64,
     P, P, P, P, I64, P)
+sig("tvq_prior_lf_eval_sample_cfg", P, I64, I64, I64, P, I64, I64, P, I64, I64, F32, F32, I64, P, P,
+    U64, P, P, P, P, I64, P)
 sig("tvq_maskgit_sample", P, I64, I64, I64, I64, I64, P, I64, P, P, U64, P, P, P)
 sig("tvq_tied_logits_sample_workspace", I64, I64, I64, restype=I64)
 sig("tvq_tied_logits_sample", P, I64, I64, P, I64, P, I64, I64, P, I64, P, P, U64, P, P, P, P, P)
+sig("tvq_tied_logits_sample_cfg", P, P, I64, I64, P, I64, P, I64, I64, F32, P, I64, P, P, U64, P, P,
+    P, P, P)
 sig("tvq_maskgit_remask", P, I64, I64, I64, F32, P, P, U64, P, I64, P, P, P)
 sig("tvq_conv_packcache_begin", I64, P, I64, P)
 sig("tvq_conv_packcache_end")

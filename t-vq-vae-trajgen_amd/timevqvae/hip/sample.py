@@ -50,6 +50,18 @@ def maskgit_sample(logits, s, mask_id, gumbel=None, site=0):
 _tls_ws = {}
 
 
+def _tls_workspace(dev, K, D, nb):
+    key = (dev, K, D, nb)
+    ws = _tls_ws.get(key)
+    if ws is None:
+        nbytes = value("tvq_tied_logits_sample_workspace", K, D, nb)
+        if nbytes < 0:
+            raise ValueError("tied_logits_sample: unsupported shape")
+        ws = torch.empty((nbytes + 15) // 16 * 4, device=dev, dtype=torch.float32)
+        _tls_ws[key] = ws
+    return ws
+
+
 def tied_logits_sample(h, W, bias, K, s, mask_id, gumbel=None, site=0, want_logits=False):
     """maskgit_sample(h @ W[:K]^T + bias[:, :K], s, mask_id) in one pass: the tied logits of
     the prior's head (bidirectional_transformer.py:186-191) computed on MFMA and consumed by
@@ -62,14 +74,7 @@ def tied_logits_sample(h, W, bias, K, s, mask_id, gumbel=None, site=0, want_logi
     s = s.contiguous()
     dev = h.device
     nb = bias.shape[0]
-    key = (dev, K, D, nb)
-    ws = _tls_ws.get(key)
-    if ws is None:
-        nbytes = value("tvq_tied_logits_sample_workspace", K, D, nb)
-        if nbytes < 0:
-            raise ValueError("tied_logits_sample: unsupported shape")
-        ws = torch.empty((nbytes + 15) // 16 * 4, device=dev, dtype=torch.float32)
-        _tls_ws[key] = ws
+    ws = _tls_workspace(dev, K, D, nb)
     sampled = torch.empty_like(s)
     selp = torch.empty((B, n), device=dev, dtype=torch.float32)
     logits = torch.empty((B, n, K), device=dev, dtype=torch.float32) if want_logits else None
@@ -77,6 +82,35 @@ def tied_logits_sample(h, W, bias, K, s, mask_id, gumbel=None, site=0, want_logi
     off = rng.call_offset(site) if gumbel is None else 0
     call("tvq_tied_logits_sample", ptr(h2), M, D, ptr(W.contiguous()), K, ptr(bias), nb,
          bias.stride(0), ptr(s), int(mask_id),
+         ptr(gumbel.contiguous() if gumbel is not None else None), ptr(seed), off,
+         ptr(sampled), ptr(selp), ptr(logits), ptr(ws), stream_ptr())
+    return (sampled, selp, logits) if want_logits else (sampled, selp)
+
+
+def tied_logits_sample_cfg(h_cond, h_null, W, bias, K, s, mask_id, cfg_scale, gumbel=None,
+                           site=0, want_logits=False):
+    """tied_logits_sample on the classifier-free-guidance mix (maskgit.py:136-153):
+    l_null + cfg_scale * (l_cond - l_null) with l_x = h_x @ W[:K]^T + bias[:, :K], the code
+    table read once for both branches and neither branch's logits written
+    (tvq_tied_logits_sample_cfg).  h_cond, h_null (B, n, D); the logits returned with
+    want_logits are the mix."""
+    if h_cond.shape != h_null.shape:
+        raise ValueError("tied_logits_sample_cfg: h_cond and h_null differ in shape")
+    B, n, D = h_cond.shape
+    M = B * n
+    hc = h_cond.reshape(M, D).contiguous()
+    hn = h_null.reshape(M, D).contiguous()
+    s = s.contiguous()
+    dev = hc.device
+    nb = bias.shape[0]
+    ws = _tls_workspace(dev, K, D, nb)
+    sampled = torch.empty_like(s)
+    selp = torch.empty((B, n), device=dev, dtype=torch.float32)
+    logits = torch.empty((B, n, K), device=dev, dtype=torch.float32) if want_logits else None
+    seed = rng.seed_tensor(dev) if gumbel is None else None
+    off = rng.call_offset(site) if gumbel is None else 0
+    call("tvq_tied_logits_sample_cfg", ptr(hc), ptr(hn), M, D, ptr(W.contiguous()), K, ptr(bias),
+         nb, bias.stride(0), float(cfg_scale), ptr(s), int(mask_id),
          ptr(gumbel.contiguous() if gumbel is not None else None), ptr(seed), off,
          ptr(sampled), ptr(selp), ptr(logits), ptr(ws), stream_ptr())
     return (sampled, selp, logits) if want_logits else (sampled, selp)

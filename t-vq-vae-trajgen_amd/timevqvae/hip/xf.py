@@ -763,12 +763,18 @@ def prior_lf_eval(tf, s, class_idx=None):
 
 
 def prior_lf_eval_sample(tf, s, class_idx, mask_id, gumbel=None, site=0, want_logits=False,
-                         ws=None, ready=False):
+                         ws=None, ready=False, cfg_scale=None):
     """prior_lf_eval + hip.sample.maskgit_sample in ONE launch: the tied logits are drawn
     from by the race in registers and never written (tvq_prior_lf_eval_sample).  Returns
     (sampled, p(sampled)[, logits]).  ws / ready: a workspace from an earlier call with the
-    same weights (ready=True skips packing them again: the decoding steps after the first)."""
+    same weights (ready=True skips packing them again: the decoding steps after the first).
+    cfg_scale (a float): classifier-free guidance in the same launch -- the draw is from
+    logits_null + cfg_scale * (logits - logits_null), both branches computed side by side
+    (tvq_prior_lf_eval_sample_cfg; class_idx required; the logits returned are the mix).
+    The workspace is the same for both forms."""
     from . import rng
+    if cfg_scale is not None and class_idx is None:
+        raise ValueError("prior_lf_eval_sample: cfg_scale needs class_idx")
     s, cls, arr, depth, K, ws = _prior_lf_args(tf, s, class_idx, ws)
     B, n = s.shape
     dev = s.device
@@ -777,10 +783,14 @@ def prior_lf_eval_sample(tf, s, class_idx, mask_id, gumbel=None, site=0, want_lo
     logits = torch.empty((B, n, K), device=dev, dtype=torch.float32) if want_logits else None
     seed = rng.seed_tensor(dev) if gumbel is None else None
     off = rng.call_offset(site) if gumbel is None else 0
-    call("tvq_prior_lf_eval_sample", ptr(s), B, n, s.stride(0), ptr(cls), tf.n_classes, 128, arr,
-         depth, K, float(tf.pred_head[2].eps), int(mask_id),
-         ptr(gumbel.contiguous() if gumbel is not None else None), ptr(seed), off,
-         ptr(sampled), ptr(selp), ptr(logits), ptr(ws), int(bool(ready)), stream_ptr())
+    head = (ptr(s), B, n, s.stride(0), ptr(cls), tf.n_classes, 128, arr, depth, K,
+            float(tf.pred_head[2].eps))
+    tail = (int(mask_id), ptr(gumbel.contiguous() if gumbel is not None else None), ptr(seed),
+            off, ptr(sampled), ptr(selp), ptr(logits), ptr(ws), int(bool(ready)), stream_ptr())
+    if cfg_scale is None:
+        call("tvq_prior_lf_eval_sample", *head, *tail)
+    else:
+        call("tvq_prior_lf_eval_sample_cfg", *head, float(cfg_scale), *tail)
     return (sampled, selp, logits) if want_logits else (sampled, selp)
 
 

@@ -35,7 +35,8 @@ from ..hip.xf import (attn_branch, attn_branch_supported, batch_colsum, drop_fir
                       prior_lf_eval_supported, prior_lf_eval_workspace, qkv_attention, rmsnorm, rmsnorm_res,
                       upsample_nearest_t)
 from ..hip._native import call, grad_sink, ptr, stream_ptr, value
-from ..hip.sample import codebook_gather_nchw, full_tokens, maskgit_sample, tied_logits_sample
+from ..hip.sample import (codebook_gather_nchw, full_tokens, maskgit_sample, tied_logits_sample,
+                          tied_logits_sample_cfg)
 from ..hip.upscale import supported as ups_supported
 from ..hip.upscale import (hf_embed_folded, hf_embed_supported, upsample_conv_gelu,
                            upsample_conv_gelu_bn_eval)
@@ -568,8 +569,22 @@ class BidirectionalTransformer(nn.Module):
         embed = embed_assemble(cls_emb, tl, th, self.pos_emb.weight, n)
         return self._blocks_head(embed)
 
+    def _lf_draw_fused(self, s_M_l):
+        return self.kind == "lf" and FUSED_SAMPLE and prior_lf_eval_supported(self, s_M_l)
+
+    def _hf_draw_fused(self):
+        return (self.kind == "hf" and not self.training and FUSED_SAMPLE
+                and self.tok_emb_h.weight.shape[1] in (64, 128))
+
+    def guided_sample_supported(self, s_M_l, s_M_h=None):
+        """Whether sample(..., cfg_scale != 1) with a class draws from the guided logits inside
+        a fused launch (tvq_prior_lf_eval_sample_cfg / tvq_tied_logits_sample_cfg).  Where it
+        does not (FUSED_SAMPLE off, training mode, unsupported shapes) the caller mixes the
+        two forwards' logits itself (MaskGIT.sample_tokens)."""
+        return self._lf_draw_fused(s_M_l) if self.kind == "lf" else self._hf_draw_fused()
+
     def sample(self, s_M_l, s_M_h=None, class_condition=None, mask_id=None, gumbel=None,
-               site=0, want_logits=False, first=True):
+               site=0, want_logits=False, first=True, cfg_scale=1.0):
         """One categorical draw per token of this prior's logits (maskgit.py:302-326): the
         sampled codes (known tokens -- the ones != mask_id of the band being decoded -- kept)
         and p(sampled) (+inf for known tokens).  The HF prior in eval mode draws straight
@@ -577,9 +592,15 @@ class BidirectionalTransformer(nn.Module):
         otherwise the logits are formed and hip.sample.maskgit_sample draws from them.
         want_logits: also return the logits (tests).  first=False: the weights are those of
         the previous call (the decoding steps after a pass's first), so the LF launch reuses
-        their packed copy."""
+        their packed copy.
+        cfg_scale != 1 with a class (classifier-free guidance, maskgit.py:136-153): where
+        guided_sample_supported, the draw is from logits_null + cfg_scale * (logits -
+        logits_null) inside the same launches, one RNG offset per call as without guidance;
+        elsewhere this method has no guided draw and says so (MaskGIT.sample_tokens mixes the
+        two forwards' logits itself then)."""
         s = s_M_l if self.kind == "lf" else s_M_h
-        if self.kind == "lf" and FUSED_SAMPLE and prior_lf_eval_supported(self, s_M_l):
+        guided = class_condition is not None and cfg_scale != 1.0
+        if self._lf_draw_fused(s_M_l):
             key = (s_M_l.device, s_M_l.shape[1])
             ws = self._eval_ws.get(key)
             fresh = ws is None
@@ -588,12 +609,26 @@ class BidirectionalTransformer(nn.Module):
                 self._eval_ws[key] = ws
             return prior_lf_eval_sample(self, s_M_l, class_condition, mask_id, gumbel=gumbel,
                                         site=site, want_logits=want_logits, ws=ws,
-                                        ready=not (first or fresh))
-        if (self.kind == "hf" and not self.training and FUSED_SAMPLE
-                and self.tok_emb_h.weight.shape[1] in (64, 128)):
+                                        ready=not (first or fresh),
+                                        cfg_scale=float(cfg_scale) if guided else None)
+        if self._hf_draw_fused():
+            if guided:
+                # both branches' head outputs in one pass on the doubled batch (eval mode:
+                # every op is per sample), the class rows cat(y, null)
+                B = s_M_h.shape[0]
+                y = class_condition.long().reshape(B, 1)
+                h = self._head_hf_eval(torch.cat((s_M_l, s_M_l)), torch.cat((s_M_h, s_M_h)),
+                                       torch.cat((y, torch.full_like(y, self.n_classes))))
+                return tied_logits_sample_cfg(h[:B], h[B:], self.tok_emb_h.weight, self.bias,
+                                              self.codebook_size, s, mask_id, float(cfg_scale),
+                                              gumbel=gumbel, site=site, want_logits=want_logits)
             return tied_logits_sample(self._head_hf_eval(s_M_l, s_M_h, class_condition),
                                       self.tok_emb_h.weight, self.bias, self.codebook_size, s,
                                       mask_id, gumbel=gumbel, site=site, want_logits=want_logits)
+        if guided:
+            raise ValueError("BidirectionalTransformer.sample: no fused guided draw for this "
+                             "prior / mode (guided_sample_supported); mix the logits of the two "
+                             "forwards as MaskGIT.sample_tokens does")
         logits = self(s_M_l, s_M_h, class_condition) if self.kind == "hf" else \
             self(s_M_l, class_condition=class_condition)
         out = maskgit_sample(logits, s, mask_id, gumbel=gumbel, site=site)
@@ -641,7 +676,7 @@ class BidirectionalTransformer(nn.Module):
         if class_condition is None:
             idx = full_tokens((B, 1), self.n_classes, dev)
         else:
-            idx = class_condition.long()
+            idx = class_condition.long()  # an explicit n_classes selects the null row
         x = embed_assemble(embedding(idx, C), u.transpose(1, 2), None, P, n)
         x = self.blocks.post_emb_norm(x)
         x = self.blocks.attn_layers(x)

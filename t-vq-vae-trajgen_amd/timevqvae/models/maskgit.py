@@ -244,13 +244,17 @@ class MaskGIT(nn.Module):
                       want_logits=False, first=True):
         """The categorical draw of one decoding step (maskgit.py:302-326): masked_prediction's
         logits -> Categorical(logits).sample() -> (sampled with known tokens kept,
-        p(sampled)).  Without guidance (cfg 1 or no class) the prior draws straight from its
-        head (BidirectionalTransformer.sample); with guidance the two forwards' logits are
-        mixed first."""
-        if class_condition is None or self.cfg_scale == 1.0:
+        p(sampled)).  The prior draws straight from its head (BidirectionalTransformer.sample):
+        without guidance (cfg 1 or no class) from its own logits, with guidance from
+        logits_null + cfg_scale * (logits - logits_null) formed inside the same launches.
+        Where the prior has no fused guided draw (guided_sample_supported: FUSED_SAMPLE off,
+        training mode, unsupported shapes) masked_prediction's mixed logits are drawn from."""
+        if (class_condition is None or self.cfg_scale == 1.0
+                or transformer.guided_sample_supported(*s_in)):
             return transformer.sample(*s_in, class_condition=class_condition, mask_id=mask_id,
                                       gumbel=gumbel, site=self._site_sample,
-                                      want_logits=want_logits, first=first)
+                                      want_logits=want_logits, first=first,
+                                      cfg_scale=self.cfg_scale)
         logits = self.masked_prediction(transformer, class_condition, *s_in)
         out = maskgit_sample(logits, s_in[-1], mask_id, gumbel=gumbel, site=self._site_sample)
         return out + (logits,) if want_logits else out
