@@ -47,6 +47,7 @@
 #include "tvq_common.h"
 #include "tvq_conv_internal.h"
 #include "tvq_reduce.h"
+#include "tvq_resblock_w8.h"
 
 namespace tvq {
 
@@ -1048,36 +1049,6 @@ static bool rb_wext(int64_t B, int64_t C, int64_t W) {
   const int64_t pl = B * C * 3 * W;
   return 2 * pl + conv_wgrad_w16_slab_floats(B, C, C) <= B * C * (9 * C + 1);
 }
-
-// the LF band's 64-channel ResBlock on (B, 64, 3, 8) (tvq_resblock_w8.hip)
-bool w8_supported(int64_t B, int64_t C, int64_t H, int64_t W);
-int64_t w8_workspace(int64_t B);
-int64_t w8_saved_floats(int64_t B);
-int w8_train_fwd(const float* x, int64_t B, const float* a1, const float* w1, const float* b1,
-                 const float* bn_w, const float* bn_b, float* running_mean, float* running_var,
-                 int64_t* nbt, float momentum, float eps, const float* a2, const float* w2,
-                 const float* b2, float drop_p, const int64_t* seed_ptr, uint64_t offset,
-                 float* saved, float* y, float* save, void* workspace, hipStream_t st);
-int w8_eval_fwd(const float* x, int64_t B, const float* a1, const float* w1, const float* b1,
-                const float* bn_w, const float* bn_b, const float* running_mean,
-                const float* running_var, float eps, const float* a2, const float* w2,
-                const float* b2, float* y, hipStream_t st);
-int w8_bwd(const float* dy, const float* x, const float* saved, int64_t B, const float* a1,
-           const float* w1, const float* bn_w, const float* save, const float* a2,
-           const float* w2, float drop_p, const int64_t* seed_ptr, uint64_t offset, float* dx,
-           float* da1, float* dw1, float* db1, float* dbn_w, float* dbn_b, float* da2, float* dw2,
-           float* db2, int64_t accumulate, void* workspace, hipStream_t st);
-int w8_pair_train_fwd(const float* x, int64_t B, const float* const* p1, const float* const* p2,
-                      float* const* rs1, float* const* rs2, int64_t* nbt1, int64_t* nbt2,
-                      float momentum, float eps, float drop_p, const int64_t* seed_ptr,
-                      uint64_t off1, uint64_t off2, float* saved1, float* y1, float* save1,
-                      float* saved2, float* y2, float* save2, void* ws1, void* ws2,
-                      hipStream_t st);
-int w8_pair_bwd(const float* dy, const float* x, int64_t B, const float* const* q1,
-                const float* const* q2, const float* saved1, const float* y1,
-                const float* saved2, float drop_p, const int64_t* seed_ptr, uint64_t off1,
-                uint64_t off2, float* dx, float* dy1, float* const* g1, float* const* g2,
-                int64_t accumulate, void* ws1, void* ws2, hipStream_t st);
 
 static RBArgs rb_fwd_args(const float* x, int64_t B, int64_t C, int64_t W, const float* a1,
                           const float* w1, const float* b1, const float* bn_w, const float* bn_b,

@@ -1,6 +1,6 @@
 """Fused ResBlock (csrc/tvq_resblock.hip, C in {8, 16, 32}; tvq_resblock_w8.hip, C = 64 on
 the LF band's W = 8 maps; tvq_resblock_w8p.hip, the projection blocks 64 -> 128 and 128 -> 64
-on those maps) against the per-op HIP path it
+on those maps; both on the stage bodies of tvq_resblock_w8_core.h) against the per-op HIP path it
 replaces (Snake -> conv -> BN+Snake -> conv+dropout+residual kernels, which the G3 goldens
 pin to the reference): training forward (y, BN running stats), every gradient, the same
 dropout mask, and the eval forward.  Tolerance: rel 2e-5 of each tensor's max (different
@@ -11,7 +11,8 @@ import torch
 pytestmark = pytest.mark.gpu
 
 SHAPES = [(8, 8, 64), (8, 16, 32), (4, 16, 16), (16, 8, 32), (3, 32, 16), (2, 32, 32),
-          (2, 16, 64), (5, 8, 16), (8, 64, 8), (3, 64, 8), (300, 64, 8)]
+          (2, 16, 64), (5, 8, 16), (8, 64, 8), (3, 64, 8), (300, 64, 8),
+          (1, 64, 8)]  # one image: one BN chunk
 
 
 def _block(C, drop, seed=0, Co=None):
@@ -90,7 +91,7 @@ def test_fused_resblock_train_matches_per_op(B, C, W, drop):
 
 
 PAIR_SHAPES = [(8, 8, 64), (8, 16, 32), (4, 16, 16), (3, 32, 16), (2, 32, 32), (5, 8, 16),
-               (8, 64, 8), (3, 64, 8), (256, 64, 8),
+               (8, 64, 8), (3, 64, 8), (256, 64, 8), (1, 64, 8),
                (32, 32, 16), (256, 32, 16)]  # B % 16 == 0: RB<32,16> external weight gradients
 
 
@@ -198,7 +199,8 @@ def test_fused_resblock_declines_unsupported_shapes():
     assert not resblock.supported(torch.empty(2, 8, 3, 32, device="cuda"), 8, 16)
 
 
-PROJ_SHAPES = [(8, 64, 128), (3, 128, 64), (256, 64, 128), (256, 128, 64), (37, 64, 128)]
+PROJ_SHAPES = [(8, 64, 128), (3, 128, 64), (256, 64, 128), (256, 128, 64), (37, 64, 128),
+               (1, 64, 128), (1, 128, 64)]  # one image: one BN chunk
 
 
 @pytest.mark.parametrize("B,Ci,Co", PROJ_SHAPES)
