@@ -237,10 +237,11 @@ __device__ __forceinline__ void pe_stream_begin(PeStream& st) {
   for (int i = 0; i < PE_PRE; ++i) st.pre[i] = st.src[i * 64 + st.lane];
 }
 
-// acc += over NS MFMA steps t of the stream's current tile: (WA) A = W[row][kmap(t,h)],
-// B = bv(t);  (!WA) A = bv(t), B = W[row][kmap(t,h)];  kmap(t,h) = 32*(t>>4) + crow(t&15, h).
-template <bool WA, int NS, class BV>
-__device__ __forceinline__ floatx16 pe_gemm(PeStream& st, BV bv, floatx16 acc) {
+// acc[nb] += over NS MFMA steps t of the stream's current tile, the tile read once for the NB
+// chains: (WA) A = W[row][kmap(t,h)], B = bv(nb, t);  (!WA) A = bv(nb, t),
+// B = W[row][kmap(t,h)];  kmap(t,h) = 32*(t>>4) + crow(t&15, h).
+template <bool WA, int NS, int NB, class BV>
+__device__ __forceinline__ void pe_gemm(PeStream& st, BV bv, floatx16 (&acc)[NB]) {
   constexpr int G = NS / 4;  // 16-B groups of the tile (>= 8)
   static_assert(G >= PE_PRE, "tile shorter than the prefetch");
   // wave-uniform tile offset in an SGPR: every load below is scalar base + the lane's
@@ -265,16 +266,25 @@ __device__ __forceinline__ floatx16 pe_gemm(PeStream& st, BV bv, floatx16 acc) {
     const float4 w4 = T4 < PE_PRE ? st.pre[T4] : rest[T4 - PE_PRE];
     const float wv[4] = {w4.x, w4.y, w4.z, w4.w};
 #pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const float b = bv(4 * T4 + e);
-      acc = WA ? pe_mfma(wv[e], b, acc) : pe_mfma(b, wv[e], acc);
-    }
+    for (int e = 0; e < 4; ++e)
+#pragma unroll
+      for (int nb = 0; nb < NB; ++nb) {
+        const float b = bv(nb, 4 * T4 + e);
+        acc[nb] = WA ? pe_mfma(wv[e], b, acc[nb]) : pe_mfma(b, wv[e], acc[nb]);
+      }
   }
 #pragma unroll
   for (int i = 0; i < PE_PRE; ++i) st.pre[i] = nq[i];
   st.off = noff;
   st.idx = nidx;
-  return acc;
+}
+
+// one chain: acc += the tile times bv(t)
+template <bool WA, int NS, class BV>
+__device__ __forceinline__ floatx16 pe_gemm(PeStream& st, BV bv, floatx16 acc) {
+  floatx16 a1[1] = {acc};
+  pe_gemm<WA, NS, 1>(st, [&](int, int t) { return bv(t); }, a1);
+  return a1[0];
 }
 
 // x-transformers RMSNorm (rmsnorm_fwd_kernel): x * (1 / max(|x|, 1e-12)) * sqrt(D) * g;
@@ -356,36 +366,86 @@ __device__ __forceinline__ void pe_layernorm(floatx16 (&x)[4], const float* __re
     }
 }
 
-// The tied logits + race of the one-wave kernel; the variants are compile-time so the
-// product path (device noise, no logits copy) has no branch in its loop.  (Software-
-// pipelining tile c + 1's MFMA chain against tile c's race in one basic block measured
-// slower: 328 vs 317 us per launch, the extra live accumulator pushing values into AGPR
-// moves.)  lout (tests): the logits.
-template <bool INJ, bool LOUT>
-__device__ __forceinline__ void pe_draw(PeStream& st, const floatx16 (&x)[4], RaceState& rs,
-                                        const float* __restrict__ brow,
-                                        const float* __restrict__ grow, uint32_t key,
-                                        uint32_t ctr0, float* __restrict__ lout, bool store_ok,
-                                        int K, int h) {
-  auto bx = [&](int tt) { return x[tt >> 4][tt & 15]; };
-  for (int c0 = 0; c0 < K; c0 += 32) {
+// ---- the draw of both sampling kernels: tied logits token-on-the-lane (the code tile as the
+// A operand: registers = codes crow(r, h)), drawn from by the race in registers (tvq_race.h).
+
+// A lane's token in the draw: lane r32 holds token r32 of sequence b, the cls token first,
+// so tokens 1..n draw.  The cls and the padding lanes run along (the MFMA chains need every
+// lane) on clamped, valid rows -- race_tile<true> dereferences grow unconditionally -- and
+// store nothing.
+struct PeTok {
+  bool ok;            // a token that draws
+  int64_t t;          // its row of sampled, selp, gumbel and logits
+  const float* brow;  // its bias row
+  const float* grow;  // its noise row, or null
+  float* lout;        // its logits row, or null
+  uint32_t key, ctr0;
+};
+__device__ __forceinline__ PeTok pe_tok(const PriorArgs& a, int b, int r32) {
+  PeTok k;
+  k.ok = r32 >= 1 && r32 <= a.n;
+  k.t = (int64_t)b * a.n + (k.ok ? r32 - 1 : 0);
+  k.brow = a.bias + (int64_t)(k.ok ? r32 - 1 : 0) * (a.K + 1);
+  k.grow = a.gumbel ? a.gumbel + k.t * a.K : nullptr;
+  k.lout = a.logits ? a.logits + k.t * a.K : nullptr;
+  k.key = a.gumbel ? 0u : race_key(mix_seed(a.seed_ptr, a.offset));
+  k.ctr0 = (uint32_t)k.t * (uint32_t)a.K;
+  return k;
+}
+
+// The code tiles [c_lo, c_hi) (codes, multiples of 32) of the stream raced into rs.  NB = 1:
+// the logits of hb(0, t).  NB = 2 (guidance): a tile is loaded once for two MFMA chains,
+// B = hb(0, t) of the class branch and hb(1, t) of the null branch, and the race runs on
+// logits_null + scale * (logits - logits_null), formed in fp32.  The variants are compile-
+// time so the product path (device noise, no logits copy) has no branch in its loop.
+// (Software-pipelining tile c + 1's MFMA chain against tile c's race in one basic block
+// measured slower: 328 vs 317 us per launch, the extra live accumulator pushing values into
+// AGPR moves.)  lout (tests): the logits.
+template <bool INJ, bool LOUT, int NB, class HB>
+__device__ __forceinline__ void pe_draw(PeStream& st, HB hb, float scale, RaceState& rs,
+                                        const PeTok& k, int c_lo, int c_hi, int K, int h) {
+  for (int c0 = c_lo; c0 < c_hi; c0 += 32) {
     float v[16];  // the bias first: loads return in order, the stream prefetch comes next
 #pragma unroll
-    for (int r = 0; r < 16; ++r) v[r] = brow[min(c0 + race_crow(r, h), K - 1)];
-    floatx16 acc;
-    pe_zero(acc);
-    acc = pe_gemm<true, 64>(st, bx, acc);
+    for (int r = 0; r < 16; ++r) v[r] = k.brow[min(c0 + race_crow(r, h), K - 1)];
+    floatx16 acc[NB];
 #pragma unroll
-    for (int r = 0; r < 16; ++r) v[r] += acc[r];
+    for (int nb = 0; nb < NB; ++nb) pe_zero(acc[nb]);
+    pe_gemm<true, 64, NB>(st, hb, acc);
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const float bias = v[r];
+      v[r] = bias + acc[0][r];
+      if constexpr (NB == 2) {
+        const float ln = bias + acc[1][r];
+        v[r] = ln + scale * (v[r] - ln);
+      }
+    }
     if (LOUT) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int code = c0 + race_crow(r, h);
-        if (store_ok && code < K) lout[code] = v[r];
+        if (k.ok && code < K) k.lout[code] = v[r];
       }
     }
-    race_tile<INJ>(rs, v, c0, h, K, grow, key, ctr0);
+    race_tile<INJ>(rs, v, c0, h, K, k.grow, k.key, k.ctr0);
   }
+}
+
+// pe_draw's variant, chosen on wave-uniform arguments only (the MFMA chains inside need every
+// lane); the cls / padding lanes' logits stores are predicated off inside
+template <int NB, class HB>
+__device__ __forceinline__ void pe_draw_variant(const PriorArgs& a, PeStream& st, HB hb,
+                                                float scale, RaceState& rs, const PeTok& k,
+                                                int c_lo, int c_hi, int h) {
+  if (!a.gumbel && !a.logits)
+    pe_draw<false, false, NB>(st, hb, scale, rs, k, c_lo, c_hi, a.K, h);
+  else if (!a.gumbel)
+    pe_draw<false, true, NB>(st, hb, scale, rs, k, c_lo, c_hi, a.K, h);
+  else if (!a.logits)
+    pe_draw<true, false, NB>(st, hb, scale, rs, k, c_lo, c_hi, a.K, h);
+  else
+    pe_draw<true, true, NB>(st, hb, scale, rs, k, c_lo, c_hi, a.K, h);
 }
 
 // The trunk of one wave: sequence b from the embedding to pred_head's LayerNorm.  On return
@@ -531,45 +591,21 @@ __global__ __launch_bounds__(64) void prior_lf_eval_kernel(PriorArgs a,
   PeStream st;
   floatx16 x[4];
   pe_trunk(a, wstream, b, l, false, st, x);
-  const int ldb = a.K + 1;
   if (a.sampled) {
-    // ---- tied logits token-on-the-lane (the code tile as the A operand: registers = codes
-    // crow(r, h)), drawn from by the race in registers (tvq_race.h); the cls lane and the
-    // padding lanes run along and store nothing
-    const int tok = r32;
-    const bool tok_ok = tok >= 1 && tok <= n;
-    const int64_t t = (int64_t)b * n + (tok_ok ? tok - 1 : 0);
-    const float* brow = a.bias + (int64_t)(tok_ok ? tok - 1 : 0) * ldb;
-    // every lane reads a valid row (t is clamped for the cls / padding lanes, which store
-    // nothing): race_tile<true> dereferences it unconditionally
-    const float* grow = a.gumbel ? a.gumbel + t * a.K : nullptr;
-    const uint32_t key = a.gumbel ? 0u : race_key(mix_seed(a.seed_ptr, a.offset));
-    // the variant is chosen on wave-uniform arguments only (the MFMA chains inside need every
-    // lane); the cls / padding lanes' logits stores are predicated off inside
-    float* lout = a.logits ? a.logits + t * a.K : nullptr;
+    const PeTok k = pe_tok(a, b, r32);
     RaceState rs;
     race_init(rs);
-    const uint32_t ctr0 = (uint32_t)t * (uint32_t)a.K;
-    if (!a.gumbel && !a.logits)
-      pe_draw<false, false>(st, x, rs, brow, nullptr, key, ctr0, nullptr, tok_ok, a.K, h);
-    else if (!a.gumbel)
-      pe_draw<false, true>(st, x, rs, brow, nullptr, key, ctr0, lout, tok_ok, a.K, h);
-    else if (!a.logits)
-      pe_draw<true, false>(st, x, rs, brow, grow, key, ctr0, nullptr, tok_ok, a.K, h);
-    else
-      pe_draw<true, true>(st, x, rs, brow, grow, key, ctr0, lout, tok_ok, a.K, h);
+    pe_draw_variant<1>(a, st, [&](int, int t) { return x[t >> 4][t & 15]; }, 0.f, rs, k, 0, a.K, h);
     int pick;
     float p;
     race_finish(rs, pick, p);
-    if (h == 0 && tok_ok) {
-      const int64_t s0 = a.s[(int64_t)b * a.ss + tok - 1];
-      const bool known = s0 != a.mask_id;
-      a.sampled[t] = known ? s0 : (int64_t)pick;
-      a.selp[t] = known ? INFINITY : p;
-    }
+    if (h == 0 && k.ok)
+      race_store(a.s[(int64_t)b * a.ss + r32 - 1], a.mask_id, pick, p, a.sampled + k.t,
+                 a.selp + k.t);
     return;
   }
   // ---- tied logits: lane = code, registers = tokens crow(r, h); the cls row is dropped
+  const int ldb = a.K + 1;
   float* out = a.logits + (int64_t)b * n * a.K;
   for (int c0 = 0; c0 < a.K; c0 += 32) {
     const int code = c0 + r32;
@@ -591,81 +627,10 @@ __global__ __launch_bounds__(64) void prior_lf_eval_kernel(PriorArgs a,
 // logits_null)) inside the draw launch.  One block of two waves per sequence: wave 0 runs the
 // trunk with the sequence's class row, wave 1 with the null-class row, from the same packed
 // stream; they meet once, when both head outputs h exist, through LDS.  Each wave then takes
-// a contiguous half of the code tiles, loads a tile once for two MFMA chains (B = h_cond,
-// B = h_null), mixes the two logits in fp32 and races on the mix with the counters of the
-// unguided draw; the waves' race states merge through LDS (race_merge is symmetric, ties to
-// the lowest code).  Neither branch's logits reach memory.
-
-// pe_gemm<true, NS> for two B operands on one pass over the tile
-template <int NS, class BC, class BN>
-__device__ __forceinline__ void pe_gemm2(PeStream& st, BC bc, BN bn, floatx16& accc,
-                                         floatx16& accn) {
-  constexpr int G = NS / 4;
-  static_assert(G >= PE_PRE, "tile shorter than the prefetch");
-  const int off = __builtin_amdgcn_readfirstlane((int)st.off);
-  const float4* cur = st.src + off;
-  float4 rest[G - PE_PRE > 0 ? G - PE_PRE : 1];
-#pragma unroll
-  for (int i = 0; i < G - PE_PRE; ++i) rest[i] = cur[(PE_PRE + i) * 64 + st.lane];
-  const int nidx = st.idx + 1;
-  const int noff = off + G * 64;
-  float4 nq[PE_PRE];
-  if (nidx < st.ntiles) {
-#pragma unroll
-    for (int i = 0; i < PE_PRE; ++i) nq[i] = st.src[noff + i * 64 + st.lane];
-  } else {
-#pragma unroll
-    for (int i = 0; i < PE_PRE; ++i) nq[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-  }
-#pragma unroll
-  for (int T4 = 0; T4 < G; ++T4) {
-    const float4 w4 = T4 < PE_PRE ? st.pre[T4] : rest[T4 - PE_PRE];
-    const float wv[4] = {w4.x, w4.y, w4.z, w4.w};
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      accc = pe_mfma(wv[e], bc(4 * T4 + e), accc);
-      accn = pe_mfma(wv[e], bn(4 * T4 + e), accn);
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < PE_PRE; ++i) st.pre[i] = nq[i];
-  st.off = noff;
-  st.idx = nidx;
-}
-
-// pe_draw on the guided mix, over the code tiles [c_lo, c_hi) (codes, multiples of 32)
-template <bool INJ, bool LOUT>
-__device__ __forceinline__ void pe_draw_cfg(PeStream& st, const float (&hc)[64],
-                                            const float (&hn)[64], float scale, RaceState& rs,
-                                            const float* __restrict__ brow,
-                                            const float* __restrict__ grow, uint32_t key,
-                                            uint32_t ctr0, float* __restrict__ lout,
-                                            bool store_ok, int c_lo, int c_hi, int K, int h) {
-  for (int c0 = c_lo; c0 < c_hi; c0 += 32) {
-    float bq[16];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) bq[r] = brow[min(c0 + race_crow(r, h), K - 1)];
-    floatx16 ac, an;
-    pe_zero(ac);
-    pe_zero(an);
-    pe_gemm2<64>(st, [&](int t) { return hc[t]; }, [&](int t) { return hn[t]; }, ac, an);
-    float v[16];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const float lc = bq[r] + ac[r], ln = bq[r] + an[r];
-      v[r] = ln + scale * (lc - ln);
-    }
-    if (LOUT) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int code = c0 + race_crow(r, h);
-        if (store_ok && code < K) lout[code] = v[r];
-      }
-    }
-    race_tile<INJ>(rs, v, c0, h, K, grow, key, ctr0);
-  }
-}
-
+// a contiguous half of the code tiles for pe_draw's two chains (B = h_cond, B = h_null) and
+// races on the mix with the counters of the unguided draw; the waves' race states merge
+// through LDS (race_merge is symmetric, ties to the lowest code).  Neither branch's logits
+// reach memory.
 __global__ __launch_bounds__(128) void prior_lf_eval_cfg_kernel(
     PriorArgs a, const float4* __restrict__ wstream, float cfg_scale) {
   __shared__ float hx[2][64][64];  // [branch][MFMA step][lane]: h of both branches
@@ -675,7 +640,6 @@ __global__ __launch_bounds__(128) void prior_lf_eval_cfg_kernel(
   const int l = threadIdx.x & 63, r32 = l & 31, h = l >> 5;
   const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));  // 0: class, 1: null
   const int b = blockIdx.x;
-  const int n = a.n;
   PeStream st;
   {
     floatx16 x[4];
@@ -684,11 +648,11 @@ __global__ __launch_bounds__(128) void prior_lf_eval_cfg_kernel(
     for (int t = 0; t < 64; ++t) hx[w][t][l] = x[t >> 4][t & 15];
   }
   __syncthreads();
-  float hc[64], hn[64];
+  float hb[2][64];  // 0: class, 1: null
 #pragma unroll
   for (int t = 0; t < 64; ++t) {
-    hc[t] = hx[0][t][l];
-    hn[t] = hx[1][t][l];
+    hb[0][t] = hx[0][t][l];
+    hb[1][t] = hx[1][t][l];
   }
   // this wave's code tiles: wave 0 [0, ceil(Kt / 2)), wave 1 the rest (none when Kt == 1).
   // The code tiles are 1024 float4 each and st stands at the first one.
@@ -704,46 +668,24 @@ __global__ __launch_bounds__(128) void prior_lf_eval_cfg_kernel(
       for (int i = 0; i < PE_PRE; ++i) st.pre[i] = st.src[st.off + i * 64 + l];
     }
   }
-  const int ldb = a.K + 1;
-  const int tok = r32;
-  const bool tok_ok = tok >= 1 && tok <= n;
-  const int64_t t = (int64_t)b * n + (tok_ok ? tok - 1 : 0);
-  // as in prior_lf_eval_kernel: every lane reads valid (clamped) rows, only token lanes store
-  const float* brow = a.bias + (int64_t)(tok_ok ? tok - 1 : 0) * ldb;
-  const float* grow = a.gumbel ? a.gumbel + t * a.K : nullptr;
-  const uint32_t key = a.gumbel ? 0u : race_key(mix_seed(a.seed_ptr, a.offset));
-  float* lout = a.logits ? a.logits + t * a.K : nullptr;
+  const PeTok k = pe_tok(a, b, r32);
   RaceState rs;
   race_init(rs);
-  const uint32_t ctr0 = (uint32_t)t * (uint32_t)a.K;
-  const int c_lo = 32 * t_lo, c_hi = 32 * t_hi;
-  if (!a.gumbel && !a.logits)
-    pe_draw_cfg<false, false>(st, hc, hn, cfg_scale, rs, brow, nullptr, key, ctr0, nullptr, tok_ok,
-                              c_lo, c_hi, a.K, h);
-  else if (!a.gumbel)
-    pe_draw_cfg<false, true>(st, hc, hn, cfg_scale, rs, brow, nullptr, key, ctr0, lout, tok_ok,
-                             c_lo, c_hi, a.K, h);
-  else if (!a.logits)
-    pe_draw_cfg<true, false>(st, hc, hn, cfg_scale, rs, brow, grow, key, ctr0, nullptr, tok_ok,
-                             c_lo, c_hi, a.K, h);
-  else
-    pe_draw_cfg<true, true>(st, hc, hn, cfg_scale, rs, brow, grow, key, ctr0, lout, tok_ok, c_lo,
-                            c_hi, a.K, h);
+  pe_draw_variant<2>(a, st, [&](int nb, int t) { return hb[nb][t]; }, cfg_scale, rs, k, 32 * t_lo,
+                     32 * t_hi, h);
   race_halves(rs);  // every lane: its token's state over this wave's codes
   if (w == 1 && h == 0) {
     mg_m[r32] = rs.m; mg_s[r32] = rs.s; mg_best[r32] = rs.best; mg_bl[r32] = rs.bl;
     mg_bk[r32] = rs.bk;
   }
   __syncthreads();
-  if (w == 0 && h == 0 && tok_ok) {
+  if (w == 0 && h == 0 && k.ok) {
     race_merge(rs, mg_m[r32], mg_s[r32], mg_best[r32], mg_bl[r32], mg_bk[r32]);
     int pick;
     float p;
     race_result(rs, pick, p);
-    const int64_t s0 = a.s[(int64_t)b * a.ss + tok - 1];
-    const bool known = s0 != a.mask_id;
-    a.sampled[t] = known ? s0 : (int64_t)pick;
-    a.selp[t] = known ? INFINITY : p;
+    race_store(a.s[(int64_t)b * a.ss + r32 - 1], a.mask_id, pick, p, a.sampled + k.t,
+               a.selp + k.t);
   }
 }
 
@@ -828,6 +770,20 @@ extern "C" int tvq_prior_lf_eval(const int64_t* s, int64_t B, int64_t n, int64_t
                               ln_eps, workspace, false, stream, "tvq_prior_lf_eval");
 }
 
+// the draw arguments of both sample entry points: checked (messages under the entry's name)
+// and put into a
+static int prior_draw_args(PriorArgs& a, const char* name, int64_t B, int64_t n, int64_t K,
+                           int64_t mask_id, const float* gumbel, const int64_t* seed_ptr,
+                           uint64_t offset, int64_t* sampled, float* selp, float* logits) {
+  TVQ_CHECK_ARG(sampled && selp, "%s: null outputs", name);
+  TVQ_CHECK_ARG(gumbel || seed_ptr, "%s: need gumbel noise or a seed", name);
+  TVQ_CHECK_ARG(gumbel || B * n * K < (int64_t)1 << 32, "%s: B n K >= 2^32", name);
+  a.logits = logits;
+  a.mask_id = mask_id; a.gumbel = gumbel; a.seed_ptr = seed_ptr; a.offset = offset;
+  a.sampled = sampled; a.selp = selp;
+  return TVQ_OK;
+}
+
 extern "C" int tvq_prior_lf_eval_sample(const int64_t* s, int64_t B, int64_t n, int64_t s_stride,
                                         const int64_t* cls_idx, int64_t n_classes, int64_t width,
                                         const float* const* weights, int64_t depth, int64_t K,
@@ -836,13 +792,10 @@ extern "C" int tvq_prior_lf_eval_sample(const int64_t* s, int64_t B, int64_t n, 
                                         int64_t* sampled, float* selp, float* logits,
                                         void* workspace, int64_t workspace_ready,
                                         tvq_stream_t stream) {
-  TVQ_CHECK_ARG(sampled && selp, "tvq_prior_lf_eval_sample: null outputs");
-  TVQ_CHECK_ARG(gumbel || seed_ptr, "tvq_prior_lf_eval_sample: need gumbel noise or a seed");
-  TVQ_CHECK_ARG(gumbel || B * n * K < (int64_t)1 << 32, "tvq_prior_lf_eval_sample: B n K >= 2^32");
   PriorArgs a = {};
-  a.logits = logits;
-  a.mask_id = mask_id; a.gumbel = gumbel; a.seed_ptr = seed_ptr; a.offset = offset;
-  a.sampled = sampled; a.selp = selp;
+  const int rc = prior_draw_args(a, "tvq_prior_lf_eval_sample", B, n, K, mask_id, gumbel, seed_ptr,
+                                 offset, sampled, selp, logits);
+  if (rc != TVQ_OK) return rc;
   TVQ_PLAN("prior_lf_eval_sample B=%lld n=%lld K=%lld", (long long)B, (long long)n, (long long)K);
   return prior_lf_eval_launch(a, s, B, n, s_stride, cls_idx, n_classes, width, weights, depth, K,
                               ln_eps, workspace, workspace_ready != 0, stream,
@@ -858,16 +811,12 @@ extern "C" int tvq_prior_lf_eval_sample_cfg(const int64_t* s, int64_t B, int64_t
                                             uint64_t offset, int64_t* sampled, float* selp,
                                             float* logits, void* workspace,
                                             int64_t workspace_ready, tvq_stream_t stream) {
-  TVQ_CHECK_ARG(sampled && selp, "tvq_prior_lf_eval_sample_cfg: null outputs");
-  TVQ_CHECK_ARG(gumbel || seed_ptr, "tvq_prior_lf_eval_sample_cfg: need gumbel noise or a seed");
-  TVQ_CHECK_ARG(gumbel || B * n * K < (int64_t)1 << 32,
-                "tvq_prior_lf_eval_sample_cfg: B n K >= 2^32");
+  PriorArgs a = {};
+  const int rc = prior_draw_args(a, "tvq_prior_lf_eval_sample_cfg", B, n, K, mask_id, gumbel,
+                                 seed_ptr, offset, sampled, selp, logits);
+  if (rc != TVQ_OK) return rc;
   TVQ_CHECK_ARG(cls_idx, "tvq_prior_lf_eval_sample_cfg: guidance needs class indices");
   TVQ_CHECK_ARG(cfg_scale - cfg_scale == 0.f, "tvq_prior_lf_eval_sample_cfg: cfg_scale must be finite");
-  PriorArgs a = {};
-  a.logits = logits;
-  a.mask_id = mask_id; a.gumbel = gumbel; a.seed_ptr = seed_ptr; a.offset = offset;
-  a.sampled = sampled; a.selp = selp;
   TVQ_PLAN("prior_lf_eval_sample_cfg B=%lld n=%lld K=%lld", (long long)B, (long long)n,
            (long long)K);
   return prior_lf_eval_launch(a, s, B, n, s_stride, cls_idx, n_classes, width, weights, depth, K,

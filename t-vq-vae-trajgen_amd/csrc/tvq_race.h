@@ -1,9 +1,9 @@
 // Exponential-race sampling of one token's code from 32-code tiles of its logits held
 // "token on the lane" (v_mfma_f32_32x32x2_f32 with the code table as the A operand: lane
 // l holds token l & 31 and, in accumulator register r, code 32 c + crow(r, l >> 5) of
-// tile c).  Shared by the fused sampling epilogues (tied_logits_sample_kernel for the HF
-// prior, prior_lf_eval_kernel for the LF prior, and their guided _cfg forms): the logits
-// never reach HBM.
+// tile c).  Shared by the fused sampling epilogues: tls_body (tvq_sample.hip, the HF prior's
+// tied_logits_sample_kernel and its guided _cfg form) and pe_draw (tvq_prior_eval.hip, the LF
+// prior's prior_lf_eval_kernel and prior_lf_eval_cfg_kernel).  The logits never reach HBM.
 //
 // Per token: the race argmax_k l_k + g_k (torch.multinomial's n_sample = 1 algorithm,
 // tvq_common.h race_gumbel; ties to the lowest code), and p(pick) of the fp32 softmax --
@@ -101,6 +101,16 @@ __device__ __forceinline__ void race_result(const RaceState& st, int& pick, floa
 __device__ __forceinline__ void race_finish(RaceState& st, int& pick, float& p) {
   race_halves(st);
   race_result(st, pick, p);
+}
+
+// the draw's two results for one token: a known token (s0 != mask_id) is kept, with
+// confidence +inf (maskgit.py:320-326)
+__device__ __forceinline__ void race_store(int64_t s0, int64_t mask_id, int pick, float p,
+                                           int64_t* __restrict__ sampled,
+                                           float* __restrict__ selp) {
+  const bool known = s0 != mask_id;
+  *sampled = known ? s0 : (int64_t)pick;
+  *selp = known ? INFINITY : p;
 }
 
 }  // namespace tvq

@@ -181,28 +181,38 @@ __global__ __launch_bounds__(256) void tls_pack_kernel(const float* __restrict__
   }
 }
 
-// one wave per 32 rows (token on the lane), the code tiles streamed through registers with
-// the next tile's operand groups loading while the current one multiplies
-template <int D, bool INJ>
-__global__ __launch_bounds__(256) void tied_logits_sample_kernel(TlsArgs a) {
+// The draw of both kernels below.  One wave per 32 rows (token on the lane), the code tiles
+// streamed through registers with the next tile's operand groups loading while the current
+// one multiplies.  NB = 1: the logits of a.h.  NB = 2, the guided draw (classifier-free
+// guidance, maskgit.py:136-153): two B-operand rows per lane, a.h of the class branch and
+// h_null of the null-class branch.  A code tile's packed halves are loaded once and feed
+// both accumulators; the bias goes onto both, logits_null + scale * (logits - logits_null)
+// is formed in fp32 and raced on with the unguided draw's counters.  Neither branch's logits
+// reach memory.
+template <int D, bool INJ, int NB>
+__device__ __forceinline__ void tls_body(const TlsArgs& a, const float* __restrict__ h_null,
+                                         float scale) {
   constexpr int G = D / 8;
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, r32 = lane & 31, h = lane >> 5;
   const int64_t m0 = ((int64_t)blockIdx.x * 4 + wid) * 32;
   if (m0 >= a.M) return;
   const bool row_ok = m0 + r32 < a.M;
   const int64_t m = row_ok ? m0 + r32 : a.M - 1;
-  // B operand of step t = 16 q + 4 g + e: h[m][32 q + 8 g + 4 h + e]
-  float xb[D / 2];
+  // B operand of step t = 16 q + 4 g + e: h[m][32 q + 8 g + 4 h + e], of either branch
+  float xb[NB][D / 2];
 #pragma unroll
   for (int q = 0; q < D / 32; ++q)
 #pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      const float4 v = *reinterpret_cast<const float4*>(a.h + m * D + 32 * q + 8 * g + 4 * h);
-      xb[16 * q + 4 * g] = v.x;
-      xb[16 * q + 4 * g + 1] = v.y;
-      xb[16 * q + 4 * g + 2] = v.z;
-      xb[16 * q + 4 * g + 3] = v.w;
-    }
+    for (int g = 0; g < 4; ++g)
+#pragma unroll
+      for (int nb = 0; nb < NB; ++nb) {
+        const float* src = nb == 0 ? a.h : h_null;
+        const float4 v = *reinterpret_cast<const float4*>(src + m * D + 32 * q + 8 * g + 4 * h);
+        xb[nb][16 * q + 4 * g] = v.x;
+        xb[nb][16 * q + 4 * g + 1] = v.y;
+        xb[nb][16 * q + 4 * g + 2] = v.z;
+        xb[nb][16 * q + 4 * g + 3] = v.w;
+      }
   const int Kp = 32 * a.Kt;
   const float* brow = a.bpk + (int64_t)(m % a.n) * Kp;
   const float* grow = a.gumbel ? a.gumbel + m * a.K : nullptr;
@@ -221,16 +231,17 @@ __global__ __launch_bounds__(256) void tied_logits_sample_kernel(TlsArgs a) {
       for (int j = 0; j < H; ++j) w[j] = a.wpk[base + j * 64];
     }
   };
-  auto mfma_half = [&](const float4 (&w)[H], int t0, floatx16 acc) {
+  auto mfma_half = [&](const float4 (&w)[H], int t0, floatx16 (&acc)[NB]) {
 #pragma unroll
     for (int j = 0; j < H; ++j) {
       const int T4 = t0 + j;
-      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(w[j].x, xb[4 * T4], acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(w[j].y, xb[4 * T4 + 1], acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(w[j].z, xb[4 * T4 + 2], acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(w[j].w, xb[4 * T4 + 3], acc, 0, 0, 0);
+      const float wv[4] = {w[j].x, w[j].y, w[j].z, w[j].w};
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+#pragma unroll
+        for (int nb = 0; nb < NB; ++nb)
+          acc[nb] = __builtin_amdgcn_mfma_f32_32x32x2f32(wv[e], xb[nb][4 * T4 + e], acc[nb], 0, 0, 0);
     }
-    return acc;
   };
   float4 wa[H], wb[H];
   load_half(wa, 0);
@@ -240,19 +251,26 @@ __global__ __launch_bounds__(256) void tied_logits_sample_kernel(TlsArgs a) {
     for (int g = 0; g < 4; ++g)
       bq[g] = *reinterpret_cast<const float4*>(brow + 32 * c + 8 * g + 4 * h);
     load_half(wb, 2 * c + 1);
-    floatx16 acc;
+    floatx16 acc[NB];
 #pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-    acc = mfma_half(wa, 0, acc);
+    for (int nb = 0; nb < NB; ++nb)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[nb][r] = 0.f;
+    mfma_half(wa, 0, acc);
     load_half(wa, 2 * c + 2);
-    acc = mfma_half(wb, H, acc);
+    mfma_half(wb, H, acc);
     float v[16];
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
-      v[4 * g] = acc[4 * g] + bq[g].x;
-      v[4 * g + 1] = acc[4 * g + 1] + bq[g].y;
-      v[4 * g + 2] = acc[4 * g + 2] + bq[g].z;
-      v[4 * g + 3] = acc[4 * g + 3] + bq[g].w;
+      const float bb[4] = {bq[g].x, bq[g].y, bq[g].z, bq[g].w};
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        v[4 * g + e] = acc[0][4 * g + e] + bb[e];
+        if constexpr (NB == 2) {
+          const float lc = v[4 * g + e], ln = acc[1][4 * g + e] + bb[e];
+          v[4 * g + e] = ln + scale * (lc - ln);
+        }
+      }
     }
     if (a.logits_out && row_ok) {
 #pragma unroll
@@ -266,19 +284,14 @@ __global__ __launch_bounds__(256) void tied_logits_sample_kernel(TlsArgs a) {
   int pick;
   float p;
   race_finish(st, pick, p);
-  if (h == 0 && row_ok) {
-    const int64_t s0 = a.s_in[m];
-    const bool known = s0 != a.mask_id;
-    a.sampled[m] = known ? s0 : (int64_t)pick;
-    a.selp[m] = known ? INFINITY : p;
-  }
+  if (h == 0 && row_ok) race_store(a.s_in[m], a.mask_id, pick, p, a.sampled + m, a.selp + m);
 }
 
-// The guided draw (classifier-free guidance, maskgit.py:136-153): tied_logits_sample_kernel
-// with two B-operand rows per lane (the class and the null-class branch's head outputs).  A
-// code tile's packed halves are loaded once and feed two accumulators; the bias goes onto
-// both, logits_null + scale * (logits - logits_null) is formed in fp32 and raced on with the
-// unguided draw's counters.  Neither branch's logits reach memory.
+template <int D, bool INJ>
+__global__ __launch_bounds__(256) void tied_logits_sample_kernel(TlsArgs a) {
+  tls_body<D, INJ, 1>(a, nullptr, 0.f);
+}
+
 struct TlsCfgArgs {
   TlsArgs t;            // t.h: the class branch
   const float* h_null;  // (M, D) the null-class branch
@@ -287,101 +300,7 @@ struct TlsCfgArgs {
 
 template <int D, bool INJ>
 __global__ __launch_bounds__(256) void tied_logits_sample_cfg_kernel(TlsCfgArgs ca) {
-  const TlsArgs& a = ca.t;
-  constexpr int G = D / 8;
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, r32 = lane & 31, h = lane >> 5;
-  const int64_t m0 = ((int64_t)blockIdx.x * 4 + wid) * 32;
-  if (m0 >= a.M) return;
-  const bool row_ok = m0 + r32 < a.M;
-  const int64_t m = row_ok ? m0 + r32 : a.M - 1;
-  // B operands of step t = 16 q + 4 g + e: h[m][32 q + 8 g + 4 h + e] of either branch
-  float xc[D / 2], xn[D / 2];
-#pragma unroll
-  for (int q = 0; q < D / 32; ++q)
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      const int64_t o = m * D + 32 * q + 8 * g + 4 * h;
-      const float4 v = *reinterpret_cast<const float4*>(a.h + o);
-      const float4 u = *reinterpret_cast<const float4*>(ca.h_null + o);
-      xc[16 * q + 4 * g] = v.x;
-      xc[16 * q + 4 * g + 1] = v.y;
-      xc[16 * q + 4 * g + 2] = v.z;
-      xc[16 * q + 4 * g + 3] = v.w;
-      xn[16 * q + 4 * g] = u.x;
-      xn[16 * q + 4 * g + 1] = u.y;
-      xn[16 * q + 4 * g + 2] = u.z;
-      xn[16 * q + 4 * g + 3] = u.w;
-    }
-  const int Kp = 32 * a.Kt;
-  const float* brow = a.bpk + (int64_t)(m % a.n) * Kp;
-  const float* grow = a.gumbel ? a.gumbel + m * a.K : nullptr;
-  const uint32_t key = a.gumbel ? 0u : race_key(mix_seed(a.seed_ptr, a.offset));
-  const uint32_t ctr0 = (uint32_t)m * (uint32_t)a.K;
-  const float scale = ca.scale;
-  RaceState st;
-  race_init(st);
-  constexpr int H = G / 2;  // half-tiles through two register buffers, as the unguided kernel
-  auto load_half = [&](float4 (&w)[H], int u) {
-    if (u < 2 * a.Kt) {
-      const int64_t base = ((int64_t)(u >> 1) * G + (u & 1) * H) * 64 + lane;
-#pragma unroll
-      for (int j = 0; j < H; ++j) w[j] = a.wpk[base + j * 64];
-    }
-  };
-  auto mfma_half = [&](const float4 (&w)[H], int t0, floatx16& ac, floatx16& an) {
-#pragma unroll
-    for (int j = 0; j < H; ++j) {
-      const int T4 = t0 + j;
-      const float wv[4] = {w[j].x, w[j].y, w[j].z, w[j].w};
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        ac = __builtin_amdgcn_mfma_f32_32x32x2f32(wv[e], xc[4 * T4 + e], ac, 0, 0, 0);
-        an = __builtin_amdgcn_mfma_f32_32x32x2f32(wv[e], xn[4 * T4 + e], an, 0, 0, 0);
-      }
-    }
-  };
-  float4 wa[H], wb[H];
-  load_half(wa, 0);
-  for (int c = 0; c < a.Kt; ++c) {
-    float4 bq[4];
-#pragma unroll
-    for (int g = 0; g < 4; ++g)
-      bq[g] = *reinterpret_cast<const float4*>(brow + 32 * c + 8 * g + 4 * h);
-    load_half(wb, 2 * c + 1);
-    floatx16 ac, an;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) ac[r] = an[r] = 0.f;
-    mfma_half(wa, 0, ac, an);
-    load_half(wa, 2 * c + 2);
-    mfma_half(wb, H, ac, an);
-    float v[16];
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      const float bb[4] = {bq[g].x, bq[g].y, bq[g].z, bq[g].w};
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const float lc = ac[4 * g + e] + bb[e], ln = an[4 * g + e] + bb[e];
-        v[4 * g + e] = ln + scale * (lc - ln);
-      }
-    }
-    if (a.logits_out && row_ok) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int code = 32 * c + race_crow(r, h);
-        if (code < a.K) a.logits_out[m * a.K + code] = v[r];
-      }
-    }
-    race_tile<INJ>(st, v, 32 * c, h, a.K, grow, key, ctr0);
-  }
-  int pick;
-  float p;
-  race_finish(st, pick, p);
-  if (h == 0 && row_ok) {
-    const int64_t s0 = a.s_in[m];
-    const bool known = s0 != a.mask_id;
-    a.sampled[m] = known ? s0 : (int64_t)pick;
-    a.selp[m] = known ? INFINITY : p;
-  }
+  tls_body<D, INJ, 2>(ca.t, ca.h_null, ca.scale);
 }
 
 }  // namespace tvq
@@ -435,43 +354,64 @@ extern "C" int64_t tvq_tied_logits_sample_workspace(int64_t K, int64_t D, int64_
   return Kt * 32 * D * 4 + n * Kt * 32 * 4;
 }
 
+template <int D>
+static void tls_run(const TlsArgs& a, const float* h_null, float scale, const float* W,
+                    const float* bias, int64_t ldb, float4* wpk, float* bpk, hipStream_t st) {
+  hipLaunchKernelGGL(tls_pack_kernel<D>, dim3((unsigned)(a.Kt + a.n)), dim3(256), 0, st, W, a.K,
+                     bias, ldb, wpk, bpk, a.Kt);
+  const dim3 grid((unsigned)((a.M + 127) / 128)), block(256);
+  if (h_null) {
+    const TlsCfgArgs ca = {a, h_null, scale};
+    if (a.gumbel) hipLaunchKernelGGL((tied_logits_sample_cfg_kernel<D, true>), grid, block, 0, st, ca);
+    else hipLaunchKernelGGL((tied_logits_sample_cfg_kernel<D, false>), grid, block, 0, st, ca);
+  } else {
+    if (a.gumbel) hipLaunchKernelGGL((tied_logits_sample_kernel<D, true>), grid, block, 0, st, a);
+    else hipLaunchKernelGGL((tied_logits_sample_kernel<D, false>), grid, block, 0, st, a);
+  }
+}
+
+// Both entry points below: the checks they share (messages under the entry's name), the
+// workspace split, the pack launch and the draw.  h_null: the guided draw's null-class rows
+// (checked by its entry), null for the unguided draw.
+static int tls_launch(const char* name, const float* h, const float* h_null, float scale,
+                      int64_t M, int64_t D, const float* W, int64_t K, const float* bias,
+                      int64_t n, int64_t ldb, const int64_t* s_in, int64_t mask_id,
+                      const float* gumbel, const int64_t* seed_ptr, uint64_t offset,
+                      int64_t* sampled, float* selp, float* logits_out, void* workspace,
+                      tvq_stream_t stream) {
+  TVQ_CHECK_ARG(h && W && bias && s_in && sampled && selp && workspace && M > 0 && K > 0 &&
+                    n > 0 && ldb >= K && (D == 64 || D == 128),
+                "%s: bad arguments (D must be 64 or 128)", name);
+  TVQ_CHECK_ARG(gumbel || seed_ptr, "%s: need gumbel noise or a seed", name);
+  TVQ_CHECK_ARG(gumbel || M * K < (int64_t)1 << 32, "%s: M * K >= 2^32", name);
+  TVQ_CHECK_ARG(((uintptr_t)h & 15) == 0 && ((uintptr_t)W & 15) == 0 &&
+                    ((uintptr_t)workspace & 15) == 0,
+                "%s: h, W and the workspace must be 16-byte aligned", name);
+  const int Kt = (int)((K + 31) / 32);
+  TlsArgs a;
+  a.h = h;
+  float4* wpk = reinterpret_cast<float4*>(workspace);
+  float* bpk = reinterpret_cast<float*>(workspace) + (int64_t)Kt * 32 * D;
+  a.wpk = wpk;
+  a.bpk = bpk;
+  a.s_in = s_in; a.gumbel = gumbel; a.seed_ptr = seed_ptr; a.offset = offset;
+  a.mask_id = mask_id; a.sampled = sampled; a.selp = selp; a.logits_out = logits_out;
+  a.M = M; a.n = (int)n; a.K = (int)K; a.Kt = Kt;
+  if (D == 128) tls_run<128>(a, h_null, scale, W, bias, ldb, wpk, bpk, (hipStream_t)stream);
+  else tls_run<64>(a, h_null, scale, W, bias, ldb, wpk, bpk, (hipStream_t)stream);
+  return TVQ_OK;
+}
+
 extern "C" int tvq_tied_logits_sample(const float* h, int64_t M, int64_t D, const float* W,
                                       int64_t K, const float* bias, int64_t n, int64_t ldb,
                                       const int64_t* s_in, int64_t mask_id, const float* gumbel,
                                       const int64_t* seed_ptr, uint64_t offset, int64_t* sampled,
                                       float* selp, float* logits_out, void* workspace,
                                       tvq_stream_t stream) {
-  TVQ_CHECK_ARG(h && W && bias && s_in && sampled && selp && workspace && M > 0 && K > 0 &&
-                    n > 0 && ldb >= K && (D == 64 || D == 128),
-                "tvq_tied_logits_sample: bad arguments (D must be 64 or 128)");
-  TVQ_CHECK_ARG(gumbel || seed_ptr, "tvq_tied_logits_sample: need gumbel noise or a seed");
-  TVQ_CHECK_ARG(gumbel || M * K < (int64_t)1 << 32, "tvq_tied_logits_sample: M * K >= 2^32");
-  TVQ_CHECK_ARG(((uintptr_t)h & 15) == 0 && ((uintptr_t)W & 15) == 0 &&
-                    ((uintptr_t)workspace & 15) == 0,
-                "tvq_tied_logits_sample: h, W and the workspace must be 16-byte aligned");
-  const int Kt = (int)((K + 31) / 32);
-  hipStream_t st = (hipStream_t)stream;
-  TlsArgs a;
-  a.h = h;
-  a.wpk = reinterpret_cast<const float4*>(workspace);
-  float* bpk = reinterpret_cast<float*>(workspace) + (int64_t)Kt * 32 * D;
-  a.bpk = bpk;
-  a.s_in = s_in; a.gumbel = gumbel; a.seed_ptr = seed_ptr; a.offset = offset;
-  a.mask_id = mask_id; a.sampled = sampled; a.selp = selp; a.logits_out = logits_out;
-  a.M = M; a.n = (int)n; a.K = (int)K; a.Kt = Kt;
-  const unsigned blocks = (unsigned)((M + 127) / 128);
-  float4* wpk = reinterpret_cast<float4*>(workspace);
-  if (D == 128) {
-    hipLaunchKernelGGL(tls_pack_kernel<128>, dim3((unsigned)(Kt + n)), dim3(256), 0, st, W, (int)K,
-                       bias, ldb, wpk, bpk, Kt);
-    if (gumbel) hipLaunchKernelGGL((tied_logits_sample_kernel<128, true>), dim3(blocks), dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((tied_logits_sample_kernel<128, false>), dim3(blocks), dim3(256), 0, st, a);
-  } else {
-    hipLaunchKernelGGL(tls_pack_kernel<64>, dim3((unsigned)(Kt + n)), dim3(256), 0, st, W, (int)K,
-                       bias, ldb, wpk, bpk, Kt);
-    if (gumbel) hipLaunchKernelGGL((tied_logits_sample_kernel<64, true>), dim3(blocks), dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((tied_logits_sample_kernel<64, false>), dim3(blocks), dim3(256), 0, st, a);
-  }
+  const int rc = tls_launch("tvq_tied_logits_sample", h, nullptr, 0.f, M, D, W, K, bias, n, ldb,
+                            s_in, mask_id, gumbel, seed_ptr, offset, sampled, selp, logits_out,
+                            workspace, stream);
+  if (rc != TVQ_OK) return rc;
   TVQ_PLAN("tied_logits_sample D=%d K=%d M=%lld", (int)D, (int)K, (long long)M);
   return launch_status("tvq_tied_logits_sample");
 }
@@ -484,42 +424,13 @@ extern "C" int tvq_tied_logits_sample_cfg(const float* h_cond, const float* h_nu
                                           uint64_t offset, int64_t* sampled, float* selp,
                                           float* logits_out, void* workspace,
                                           tvq_stream_t stream) {
-  TVQ_CHECK_ARG(h_cond && h_null && W && bias && s_in && sampled && selp && workspace && M > 0 &&
-                    K > 0 && n > 0 && ldb >= K && (D == 64 || D == 128),
-                "tvq_tied_logits_sample_cfg: bad arguments (D must be 64 or 128)");
+  TVQ_CHECK_ARG(h_null && ((uintptr_t)h_null & 15) == 0,
+                "tvq_tied_logits_sample_cfg: h_null must be non-null and 16-byte aligned");
   TVQ_CHECK_ARG(cfg_scale - cfg_scale == 0.f, "tvq_tied_logits_sample_cfg: cfg_scale must be finite");
-  TVQ_CHECK_ARG(gumbel || seed_ptr, "tvq_tied_logits_sample_cfg: need gumbel noise or a seed");
-  TVQ_CHECK_ARG(gumbel || M * K < (int64_t)1 << 32, "tvq_tied_logits_sample_cfg: M * K >= 2^32");
-  TVQ_CHECK_ARG(((uintptr_t)h_cond & 15) == 0 && ((uintptr_t)h_null & 15) == 0 &&
-                    ((uintptr_t)W & 15) == 0 && ((uintptr_t)workspace & 15) == 0,
-                "tvq_tied_logits_sample_cfg: h_cond, h_null, W and the workspace must be 16-byte "
-                "aligned");
-  const int Kt = (int)((K + 31) / 32);
-  hipStream_t st = (hipStream_t)stream;
-  TlsCfgArgs ca;
-  TlsArgs& a = ca.t;
-  a.h = h_cond;
-  ca.h_null = h_null;
-  ca.scale = cfg_scale;
-  a.wpk = reinterpret_cast<const float4*>(workspace);
-  float* bpk = reinterpret_cast<float*>(workspace) + (int64_t)Kt * 32 * D;
-  a.bpk = bpk;
-  a.s_in = s_in; a.gumbel = gumbel; a.seed_ptr = seed_ptr; a.offset = offset;
-  a.mask_id = mask_id; a.sampled = sampled; a.selp = selp; a.logits_out = logits_out;
-  a.M = M; a.n = (int)n; a.K = (int)K; a.Kt = Kt;
-  const unsigned blocks = (unsigned)((M + 127) / 128);
-  float4* wpk = reinterpret_cast<float4*>(workspace);
-  if (D == 128) {
-    hipLaunchKernelGGL(tls_pack_kernel<128>, dim3((unsigned)(Kt + n)), dim3(256), 0, st, W, (int)K,
-                       bias, ldb, wpk, bpk, Kt);
-    if (gumbel) hipLaunchKernelGGL((tied_logits_sample_cfg_kernel<128, true>), dim3(blocks), dim3(256), 0, st, ca);
-    else hipLaunchKernelGGL((tied_logits_sample_cfg_kernel<128, false>), dim3(blocks), dim3(256), 0, st, ca);
-  } else {
-    hipLaunchKernelGGL(tls_pack_kernel<64>, dim3((unsigned)(Kt + n)), dim3(256), 0, st, W, (int)K,
-                       bias, ldb, wpk, bpk, Kt);
-    if (gumbel) hipLaunchKernelGGL((tied_logits_sample_cfg_kernel<64, true>), dim3(blocks), dim3(256), 0, st, ca);
-    else hipLaunchKernelGGL((tied_logits_sample_cfg_kernel<64, false>), dim3(blocks), dim3(256), 0, st, ca);
-  }
+  const int rc = tls_launch("tvq_tied_logits_sample_cfg", h_cond, h_null, cfg_scale, M, D, W, K,
+                            bias, n, ldb, s_in, mask_id, gumbel, seed_ptr, offset, sampled, selp,
+                            logits_out, workspace, stream);
+  if (rc != TVQ_OK) return rc;
   TVQ_PLAN("tied_logits_sample_cfg D=%d K=%d M=%lld", (int)D, (int)K, (long long)M);
   return launch_status("tvq_tied_logits_sample_cfg");
 }

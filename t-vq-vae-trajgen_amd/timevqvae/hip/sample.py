@@ -62,15 +62,12 @@ def _tls_workspace(dev, K, D, nb):
     return ws
 
 
-def tied_logits_sample(h, W, bias, K, s, mask_id, gumbel=None, site=0, want_logits=False):
-    """maskgit_sample(h @ W[:K]^T + bias[:, :K], s, mask_id) in one pass: the tied logits of
-    the prior's head (bidirectional_transformer.py:186-191) computed on MFMA and consumed by
-    the race in registers, never written to memory (include/tvq.h tvq_tied_logits_sample).
-    h (B, n, D) with D 64 or 128; bias (n, ldb >= K).  want_logits: also return the logits
-    the draw used (tests)."""
+def _tied_logits_sample(h, h_null, cfg_scale, W, bias, K, s, mask_id, gumbel, site, want_logits):
+    """Both draws below.  h_null None: tvq_tied_logits_sample on h; else the guided entry on
+    (h, h_null) with cfg_scale."""
     B, n, D = h.shape
     M = B * n
-    h2 = h.reshape(M, D).contiguous()
+    hs = [t.reshape(M, D).contiguous() for t in ((h,) if h_null is None else (h, h_null))]
     s = s.contiguous()
     dev = h.device
     nb = bias.shape[0]
@@ -80,11 +77,22 @@ def tied_logits_sample(h, W, bias, K, s, mask_id, gumbel=None, site=0, want_logi
     logits = torch.empty((B, n, K), device=dev, dtype=torch.float32) if want_logits else None
     seed = rng.seed_tensor(dev) if gumbel is None else None
     off = rng.call_offset(site) if gumbel is None else 0
-    call("tvq_tied_logits_sample", ptr(h2), M, D, ptr(W.contiguous()), K, ptr(bias), nb,
-         bias.stride(0), ptr(s), int(mask_id),
+    shape = (M, D, ptr(W.contiguous()), K, ptr(bias), nb, bias.stride(0))
+    guide = () if h_null is None else (float(cfg_scale),)
+    call("tvq_tied_logits_sample" if h_null is None else "tvq_tied_logits_sample_cfg",
+         *[ptr(t) for t in hs], *shape, *guide, ptr(s), int(mask_id),
          ptr(gumbel.contiguous() if gumbel is not None else None), ptr(seed), off,
          ptr(sampled), ptr(selp), ptr(logits), ptr(ws), stream_ptr())
     return (sampled, selp, logits) if want_logits else (sampled, selp)
+
+
+def tied_logits_sample(h, W, bias, K, s, mask_id, gumbel=None, site=0, want_logits=False):
+    """maskgit_sample(h @ W[:K]^T + bias[:, :K], s, mask_id) in one pass: the tied logits of
+    the prior's head (bidirectional_transformer.py:186-191) computed on MFMA and consumed by
+    the race in registers, never written to memory (include/tvq.h tvq_tied_logits_sample).
+    h (B, n, D) with D 64 or 128; bias (n, ldb >= K).  want_logits: also return the logits
+    the draw used (tests)."""
+    return _tied_logits_sample(h, None, None, W, bias, K, s, mask_id, gumbel, site, want_logits)
 
 
 def tied_logits_sample_cfg(h_cond, h_null, W, bias, K, s, mask_id, cfg_scale, gumbel=None,
@@ -96,24 +104,8 @@ def tied_logits_sample_cfg(h_cond, h_null, W, bias, K, s, mask_id, cfg_scale, gu
     want_logits are the mix."""
     if h_cond.shape != h_null.shape:
         raise ValueError("tied_logits_sample_cfg: h_cond and h_null differ in shape")
-    B, n, D = h_cond.shape
-    M = B * n
-    hc = h_cond.reshape(M, D).contiguous()
-    hn = h_null.reshape(M, D).contiguous()
-    s = s.contiguous()
-    dev = hc.device
-    nb = bias.shape[0]
-    ws = _tls_workspace(dev, K, D, nb)
-    sampled = torch.empty_like(s)
-    selp = torch.empty((B, n), device=dev, dtype=torch.float32)
-    logits = torch.empty((B, n, K), device=dev, dtype=torch.float32) if want_logits else None
-    seed = rng.seed_tensor(dev) if gumbel is None else None
-    off = rng.call_offset(site) if gumbel is None else 0
-    call("tvq_tied_logits_sample_cfg", ptr(hc), ptr(hn), M, D, ptr(W.contiguous()), K, ptr(bias),
-         nb, bias.stride(0), float(cfg_scale), ptr(s), int(mask_id),
-         ptr(gumbel.contiguous() if gumbel is not None else None), ptr(seed), off,
-         ptr(sampled), ptr(selp), ptr(logits), ptr(ws), stream_ptr())
-    return (sampled, selp, logits) if want_logits else (sampled, selp)
+    return _tied_logits_sample(h_cond, h_null, cfg_scale, W, bias, K, s, mask_id, gumbel, site,
+                               want_logits)
 
 
 def maskgit_remask(selp, k, temperature, sampled=None, mask_id=0, u_gumbel=None, site=0,

@@ -2,7 +2,9 @@
 logits_null + cfg_scale * (logits - logits_null)): tvq_prior_lf_eval_sample_cfg (the LF
 prior, csrc/tvq_prior_eval.hip), tvq_tied_logits_sample_cfg (the HF prior's head,
 csrc/tvq_sample.hip) and their routing through BidirectionalTransformer.sample /
-MaskGIT.sample_tokens / iterative_decoding / GraphedSampler.
+MaskGIT.sample_tokens / iterative_decoding / GraphedSampler.  Each guided kernel runs the
+unguided kernel's draw body with two B operands (pe_draw / tls_body with NB = 2), so the cases
+here and in test_prior_eval / test_sampler cover one tile loop from both sides.
 
 Tolerances.  With s the scale, w(s) = |1 - s| + |s| is how the mix scales an error of its two
 inputs.  Two launches of the LF kernel agree within 1e-6 of the logit scale
@@ -100,7 +102,7 @@ def test_lf_guided_draw(depth, K, n, B, sc, cuda):
 
 
 @pytest.mark.parametrize("B,n,D,K,sc", [(3, 7, 64, 33, 2.0), (5, 13, 128, 100, 0.0),
-                                        (9, 96, 128, 512, 3.0)])
+                                        (9, 96, 128, 512, 3.0), (2, 5, 64, 20, 2.0)])
 def test_hf_guided_draw(B, n, D, K, sc, cuda):
     from timevqvae.hip import rng
     from timevqvae.hip._native import plan_trace

@@ -99,7 +99,8 @@ def test_sample_race_frequencies(cuda):
     assert float(((f - p).abs() / sig).max()) < 5.0, (f, p)
 
 
-@pytest.mark.parametrize("B,n,D,K", [(1024, 96, 128, 512), (5, 13, 128, 100), (3, 7, 64, 33)])
+@pytest.mark.parametrize("B,n,D,K", [(1024, 96, 128, 512), (5, 13, 128, 100), (3, 7, 64, 33),
+                                     (2, 5, 64, 20)])
 def test_tied_logits_sample_vs_oracle(B, n, D, K, cuda):
     """The fused head + draw (tvq_tied_logits_sample): its logits within 1e-5 of torch's
     h W[:K]^T + bias, its draw exactly the race on those logits, p(sampled) within 2e-6,
