@@ -210,7 +210,9 @@ int tvq_istft_decode_bwd(const float* dy, int64_t B, int64_t C, int64_t W, int64
  * nn.Conv2d / nn.ConvTranspose2d / nn.Conv1d of VQVAEEncBlock, ResBlock,
  * VQVAEDecBlock, the decoder tail and Upscale (vq_vae.py:13-121,238-251;
  * bidirectional_transformer.py:12-30).  NCHW fp32; supported kernels:
- * (KH,KW,SW) = (3,4,2) [replicate or zero pad], (3,3,1), (1,1,1), (1,3,1);
+ * (KH,KW,SW) = (3,4,2) [replicate or zero pad], (3,3,1), (1,1,1), (1,3,1) [replicate or
+ * zero pad], and the FidelityEnhancer's (1,7,1) and (1,4,2) [zero pad] (its init conv and
+ * Downsample; the (1,3,1) replicate form is its final convs);
  * padding (KH/2, (KW-1)/2).  Epilogue of the forward conv: + bias, optional
  * dropout (counter-based mask keyed by (*seed_ptr, offset) and the flat output
  * index: the device seed advances once per step so graph replays differ) and + residual
@@ -848,7 +850,11 @@ int tvq_fe_channel_layernorm_bwd(const float* dy, const float* x, int64_t B, int
                                  int64_t L, const float* g, float eps, float* dx, float* tg,
                                  tvq_stream_t stream);
 /* attention cores backward: qkv (B, 3 H dh, n) as to_qkv wrote it, dout (B, H dh, n) ->
- * dqkv (B, 3 H dh, n); dh = 32; full attention n <= ~70 (LDS) */
+ * dqkv (B, 3 H dh, n); dh = 32.  One block per (b, h) keeps its operands in LDS, and the
+ * launch check bounds n: linear attention 4 (96 (n + 1) + 2112) bytes <= 160 KB, n <= 403;
+ * full attention n <= 112 (158592 bytes of LDS).  A longer n is TVQ_ERR_ARG before
+ * any launch.  The forwards accept more (tvq_fe_linear_attention n <= 621,
+ * tvq_fe_attention n <= 640), so a longer sequence passes its forward and fails here. */
 int tvq_fe_linear_attention_bwd(const float* qkv, const float* dout, int64_t B, int64_t H,
                                 int64_t dh, int64_t n, float* dqkv, tvq_stream_t stream);
 int tvq_fe_attention_bwd(const float* qkv, const float* dout, int64_t B, int64_t H, int64_t dh,

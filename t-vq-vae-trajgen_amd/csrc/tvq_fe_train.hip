@@ -22,6 +22,13 @@ namespace tvq {
 namespace {
 
 constexpr int DH = 32;  // dim_head of both FidelityEnhancer attentions
+// Longest sequence of the full-attention backward (include/tvq.h): one block per (b, h) keeps
+// q, k, v, do and the two n x (n + 1) score matrices in LDS, 158592 B at n = 112 of the 160 KB
+// a block may use.  The Unet's mid attention runs at an eighth of the first level's length,
+// which the linear attention's own limit (n <= 403) holds to 50 keys.
+constexpr int ATTN_BWD_MAX_N = 112;
+constexpr size_t attn_bwd_lds(size_t n) { return (4 * n * DH + 2 * n * (n + 1)) * 4; }
+static_assert(attn_bwd_lds(ATTN_BWD_MAX_N) <= 160 * 1024, "full-attention backward LDS");
 
 // ---------------------------------------------------------------- weight standardisation
 __global__ __launch_bounds__(256) void fe_ws_bwd_kernel(const float* __restrict__ w, int n,
@@ -173,7 +180,8 @@ __global__ __launch_bounds__(256) void fe_chan_ln_bwd_kernel(const float* __rest
 
 // ---------------------------------------------------------------- linear attention core
 // One block per (b, h).  LDS: qsm (softmax over d, unscaled), ks (softmax over n), v, each
-// DH x n (row stride n+1); ctx, dctx DH x DH.  dout / outputs through global memory.
+// DH x n (row stride n+1); ctx, dctx DH x DH: 4 (96 (n + 1) + 2112) bytes, which the launch
+// check holds to 160 KB, so n <= 403.  dout / outputs through global memory.
 __global__ __launch_bounds__(256) void fe_linattn_bwd_kernel(const float* __restrict__ qkv,
                                                              const float* __restrict__ dout,
                                                              int H, int n, float scale,
@@ -278,8 +286,8 @@ __global__ __launch_bounds__(256) void fe_linattn_bwd_kernel(const float* __rest
 }
 
 // ---------------------------------------------------------------- full attention core
-// One block per (b, h); n <= 128 keys.  LDS: q*scale, k, v, do (n x DH each), P and dS
-// (n x (n+1)).
+// One block per (b, h); n <= ATTN_BWD_MAX_N = 112 keys (the launch check).  LDS: q*scale, k,
+// v, do (n x DH each), P and dS (n x (n+1)): attn_bwd_lds(n) bytes.
 __global__ __launch_bounds__(256) void fe_attn_bwd_kernel(const float* __restrict__ qkv,
                                                           const float* __restrict__ dout, int H,
                                                           int n, float scale,
@@ -485,8 +493,8 @@ extern "C" int tvq_fe_attention_bwd(const float* qkv, const float* dout, int64_t
                                     int64_t dh, int64_t n, float* dqkv, tvq_stream_t stream) {
   TVQ_CHECK_ARG(qkv && dout && dqkv && dh == DH && B > 0 && H > 0 && n > 0,
                 "tvq_fe_attention_bwd: bad arguments");
-  const size_t lds = ((size_t)4 * n * DH + 2 * n * (n + 1)) * 4;
-  TVQ_CHECK_ARG(lds <= 160 * 1024, "tvq_fe_attention_bwd: n too large");
+  TVQ_CHECK_ARG(n <= ATTN_BWD_MAX_N, "tvq_fe_attention_bwd: n too large");
+  const size_t lds = attn_bwd_lds((size_t)n);
   fe_train_lds_attr();
   hipLaunchKernelGGL(fe_attn_bwd_kernel, dim3((unsigned)(B * H)), dim3(256), lds,
                      (hipStream_t)stream, qkv, dout, (int)H, (int)n, 1.0f / sqrtf((float)DH),

@@ -121,6 +121,121 @@ def test_conv1d_k3(B, Ci, Co, cuda):
         close(d[i].grad, c[i].grad, what=n)
 
 
+# The FidelityEnhancer's Unet1D convs (models/fidelity_enhancer.py): 3-D (B, C, L) maps on
+# the conv engine as H = 1 images.  (B, Ci, Co, L, K, stride, replicate, form)
+FE_CONVS = [
+    # k7 s1 (init conv); L = 5 < K: taps hang over both ends
+    (3, 6, 8, 256, 7, 1, False, "bias"), (2, 6, 8, 301, 7, 1, False, "bias"),
+    (2, 6, 8, 5, 7, 1, False, "bias"),
+    # k4 s2 zero pad (Downsample); L = 3, 2: one output
+    (3, 8, 8, 256, 4, 2, False, "bias"), (2, 8, 8, 301, 4, 2, False, "bias"),
+    (2, 16, 16, 150, 4, 2, False, "bias"), (2, 32, 32, 75, 4, 2, False, "bias"),
+    (2, 8, 8, 3, 4, 2, False, "bias"), (2, 8, 8, 2, 4, 2, False, "bias"),
+    # k3 replicate (final convs)
+    (2, 8, 8, 301, 3, 1, True, "bias"), (2, 8, 6, 256, 3, 1, True, "bias"),
+    (2, 8, 6, 2, 3, 1, True, "bias"),
+    # k3 zero pad at the Unet's channel counts
+    (2, 96, 32, 75, 3, 1, False, "bias"), (2, 64, 64, 32, 3, 1, False, "bias"),
+    (2, 64, 64, 37, 3, 1, False, "bias"), (2, 128, 64, 37, 3, 1, False, "bias"),
+    (2, 16, 8, 301, 3, 1, False, "bias"),
+    # k1: res_conv, to_qkv (no bias), to_out with the fused residual
+    (2, 96, 32, 75, 1, 1, False, "bias"), (2, 64, 384, 37, 1, 1, False, "nobias"),
+    (2, 128, 64, 37, 1, 1, False, "residual"),
+]
+# the weight-gradient variant tvq_conv2d_wgrad takes on the default path, where the test
+# pins it: conv_wgrad_t32 needs stride 1, zero pad, K = 3, L % 32 == 0 and >= 64 channels on
+# both sides; conv_wgrad_halo needs Lout % 4 == 0 and a small C x Co; the rest is the split
+# GEMM.  All three are reachable at H = 1 (conv_wgrad_s2 and conv_wgrad_w8 need H = 3).
+FE_WGRAD = {
+    (2, 64, 64, 32, 3, 1, False, "bias"): "conv_wgrad_t32",
+    (3, 6, 8, 256, 7, 1, False, "bias"): "conv_wgrad_halo",
+    (3, 8, 8, 256, 4, 2, False, "bias"): "conv_wgrad_halo",
+    (2, 8, 6, 256, 3, 1, True, "bias"): "conv_wgrad_halo",
+    (2, 6, 8, 301, 7, 1, False, "bias"): "conv_wgrad split=",
+    (2, 8, 8, 301, 4, 2, False, "bias"): "conv_wgrad split=",
+    (2, 8, 8, 301, 3, 1, True, "bias"): "conv_wgrad split=",
+    (2, 64, 384, 37, 1, 1, False, "nobias"): "conv_wgrad split=",
+}
+WGRAD_VARIANTS = ("conv_wgrad_t32", "conv_wgrad_halo", "conv_wgrad split=", "conv_wgrad_s2",
+                  "conv_wgrad_w8")
+
+
+@pytest.mark.parametrize("case", FE_CONVS, ids=lambda c: "-".join(str(v) for v in c))
+@pytest.mark.parametrize("path", ["default", "halo", "gemm", "tap", "gemm_raw"])
+def test_conv1d_fe(case, path, cuda, conv_path):
+    """Stage 3's conv geometries, fwd / dx / dw / db against float32 CPU F.conv1d; on the
+    default path the weight-gradient dispatch of the cases in FE_WGRAD is pinned."""
+    from timevqvae.hip._native import plan_trace
+    from timevqvae.hip.conv import conv2d
+    B, Ci, Co, L, K, S, rep, form = case
+    conv_path(path)
+
+    def ref(x, w, b=None, r=None):
+        xp = F.pad(x, (1, 1), mode="replicate") if rep else x
+        y = F.conv1d(xp, w, b, stride=S, padding=0 if rep else (K - 1) // 2)
+        return y + r if r is not None else y
+
+    def hip(x, w, b=None, r=None):
+        return conv2d(x, w, b, stride_w=S, replicate=rep, residual=r)
+
+    shapes = [(B, Ci, L), (Co, Ci, K)] + ([] if form == "nobias" else [(Co,)])
+    if form == "residual":
+        shapes.append((B, Co, L))
+    with plan_trace() as tr:
+        oc, od, c, d = _run_both(hip, ref, shapes, cuda, seed=L + K)
+    assert od.shape == oc.shape
+    close(od, oc, what="fwd")
+    for i, n in enumerate(("dx", "dw", "db")[:3 - (form == "nobias")]):
+        assert d[i].grad.shape == c[i].grad.shape
+        close(d[i].grad, c[i].grad, what=n)
+    if form == "residual":  # the CPU add's gradient is the upstream gradient itself
+        assert torch.equal(d[3].grad.cpu(), c[3].grad)
+    if path == "default" and case in FE_WGRAD:
+        took = [v for v in WGRAD_VARIANTS if tr.has(v)]
+        assert took == [FE_WGRAD[case]], (took, tr.lines)
+
+
+def test_conv1d_fe_wgrad_variants_covered(cuda):
+    """The cases test_conv1d_fe pins take each weight-gradient variant reachable at H = 1."""
+    assert set(FE_WGRAD.values()) == {"conv_wgrad_t32", "conv_wgrad_halo", "conv_wgrad split="}
+    assert set(FE_WGRAD) <= set(FE_CONVS)
+
+
+# (B, C, HW, offset in floats): the scalar path (HW % 4 != 0); the float4 path; the same read
+# from a pointer that is not 16-byte aligned (scalar); HW = 1 (column sums); a few images of
+# one float4; 129 images of 4096: B HW / 8192 > 64 chunks, so the cap (3 images per chunk, 43
+# chunks)
+CHAN_SUMS = [(2, 8, 301, 0), (3, 5, 8, 0), (3, 5, 8, 1), (300, 16, 1, 0), (65, 3, 4, 0),
+             (129, 3, 4096, 0)]
+
+
+@pytest.mark.parametrize("B,C,HW,off", CHAN_SUMS)
+@pytest.mark.parametrize("accumulate", [0, 1])
+def test_channel_sum(B, C, HW, off, accumulate, cuda):
+    """tvq_channel_sum (every per-channel parameter gradient of hip/fe_train.py and the bias
+    gradients) against the float64 sum, in a fixed order: two runs are bitwise equal."""
+    from timevqvae.hip._native import call, ptr, stream_ptr, value
+    gen = torch.Generator().manual_seed(B + C + HW)
+    x = torch.randn(B, C, HW, generator=gen) + 0.5
+    out0 = torch.randn(C, generator=gen)
+    buf = torch.empty(B * C * HW + off, device=cuda)
+    xd = buf[off:].view(B, C, HW)
+    xd.copy_(x)
+    assert (xd.data_ptr() % 16 != 0) == (off % 4 != 0)
+    nws = value("tvq_channel_sum_workspace", B, C, HW)
+    assert nws >= 1
+    want = x.double().sum((0, 2)) + (out0.double() if accumulate else 0)
+    outs = []
+    for _ in range(2):
+        out = out0.to(cuda)
+        ws = torch.empty(nws, device=cuda)
+        call("tvq_channel_sum", ptr(xd), B, C, HW, ptr(out), accumulate, ptr(ws), stream_ptr())
+        torch.cuda.synchronize()
+        outs.append(out.cpu())
+    close(outs[0], want, what="channel sum")
+    assert torch.equal(outs[0], outs[1])
+
+
 def test_conv_residual_dropout(cuda):
     """Fused epilogue: out = residual + Dropout(conv + b); mask regenerated in backward."""
     from timevqvae.hip.conv import conv2d
