@@ -934,18 +934,36 @@ int tvq_hfe_assemble(const float* v, const float* R, const float* P, const float
                      int64_t m, int64_t d, float* z, tvq_stream_t stream);
 int tvq_hfe_assemble_bwd(const float* dz, int64_t B, int64_t m, int64_t d, float* dv, float* dR,
                          float* dCp, tvq_stream_t stream);
-/* The priors' training loss head in one launch (+ a count, a transpose and a final launch):
- * logits = h W[:K]^T + bias[m mod n] (bidirectional_transformer.py:186-191), the masked
- * cross-entropy of maskgit.py:183-191 and, for the backward that starts at this loss with the
- * root gradient *gscale, dlogits = keep ? 0 : (softmax - onehot(target)) * gscale / cnt and
- * dh = dlogits W[:K] -- the logits never reach memory.  h (M, 128), W (>= K, 128), bias (n,
- * ldb >= K), target int64 (M), keep bool (M); out = {loss, cnt}.  K in {64, 128, 256, 512};
- * workspace: tvq_tied_logits_ce_workspace(M, K) floats. */
+/* The priors' training loss head on the masked tokens only.
+ * tvq_masked_rows lists them: keep bool (B n); rows int32 (B n, the first cnt written) = the
+ * token ids m = b n + pos of the tokens with keep false, ordered by position, then by sample;
+ * pos_off int32 (n + 1) = each position's first list index, pos_off[n] = cnt.  One launch, no
+ * host read: cnt stays on the device.
+ * tvq_tied_logits_ce, for every listed token m = rows[r]: logits = h_m W[:K]^T + bias[m mod n]
+ * (bidirectional_transformer.py:186-191), the cross-entropy of maskgit.py:183-191 and, for the
+ * backward that starts at this loss with the root gradient *gscale, dlogits[r] = (softmax -
+ * onehot(target[m])) * gscale / cnt, hc[r] = h_m and dh[m] = dlogits[r] W[:K] -- the logits
+ * never reach memory.  dlogits (M, K) and hc (M, 128) are compact: rows at or beyond cnt are
+ * neither written nor read.  dh (M, 128) is dense, zero on the kept tokens.  h (M, 128), W
+ * (>= K, 128), bias (n, ldb >= K), target int64 (M); out = {loss, cnt}.  K in {64, 128, 256,
+ * 512}; workspace: tvq_tied_logits_ce_workspace(M, K) floats.  The launches are the same for
+ * every mask (worst-case grid), so one captured graph serves them all.
+ * tvq_tied_ce_grads, on the compact rows: dW[:K] (+)= dlogits^T hc over cnt rows (dW (>= K,
+ * 128), may be NULL) and dbias[pos][:K] (+)= the sum of dlogits rows [pos_off[pos],
+ * pos_off[pos + 1]) in row order (dbias (n, ldb), may be NULL); workspace:
+ * tvq_tied_ce_grads_workspace(M, K) floats. */
+int tvq_masked_rows(const bool* keep, int64_t B, int64_t n, int32_t* rows, int32_t* pos_off,
+                    tvq_stream_t stream);
 int64_t tvq_tied_logits_ce_workspace(int64_t M, int64_t K);
 int tvq_tied_logits_ce(const float* h, int64_t M, int64_t D, const float* W, int64_t K,
                        const float* bias, int64_t n, int64_t ldb, const int64_t* target,
-                       const bool* keep, const float* gscale, float* dlogits, float* dh,
-                       float* out, float* workspace, tvq_stream_t stream);
+                       const int32_t* rows, const int32_t* pos_off, const float* gscale,
+                       float* dlogits, float* hc, float* dh, float* out, float* workspace,
+                       tvq_stream_t stream);
+int64_t tvq_tied_ce_grads_workspace(int64_t M, int64_t K);
+int tvq_tied_ce_grads(const float* dlogits, const float* hc, const int32_t* pos_off, int64_t M,
+                      int64_t K, int64_t n, float* dW, int64_t dw_accumulate, float* dbias,
+                      int64_t ldb, int64_t db_accumulate, float* workspace, tvq_stream_t stream);
 /* out[0] = a[0] / b[0] (device scalars). */
 int tvq_scalar_ratio(const float* a, const float* b, float* out, tvq_stream_t stream);
 

@@ -24,6 +24,8 @@ struct GemmArgs {
   int kper;        // K range per split
   float* slab;     // split-K partials [split][M][N] (nullptr: write C directly)
   int* cnt;        // split-K: one counter per (m, n) tile -> the last split block finishes
+  const int* kdev = nullptr;  // optional device row count (gemm_kt_kernel only): the sum runs
+                              // over min(K, *kdev) k, shared evenly by the launch's splits
 };
 
 // XCD-aware tile map for a grid of xcd_grid(mt, nt) blocks: block b runs on XCD b % 8, so

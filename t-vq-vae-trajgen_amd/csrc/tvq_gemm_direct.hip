@@ -212,9 +212,16 @@ __global__ __launch_bounds__(256) void gemm_kt_kernel(GemmArgs g, int tiles_n, i
   const int r32 = lane & 31, h = lane >> 5;
   const int tm = tile / tiles_n, tn = tile - tm * tiles_n;
   const int m0 = tm * 32, n0 = tn * 32;
-  const int kq = g.kper / 4;
-  const int kb = z * g.kper + wid * kq;
-  const int ke = min(g.K, kb + kq);
+  // a device row count (g.kdev) shortens the sum to K = min(g.K, *kdev), its spans re-cut so
+  // that the S splits share it evenly (4 waves x an even k count each, as on the host)
+  int K = g.K, kper = g.kper;
+  if (g.kdev) {
+    K = min(K, *g.kdev);
+    kper = max(8, ((K + S - 1) / S + 7) / 8 * 8);
+  }
+  const int kq = kper / 4;
+  const int kb = z * kper + wid * kq;
+  const int ke = min(K, kb + kq);
   const int steps = kb < ke ? (ke - kb + 1) / 2 : 0;
   const float* pa = g.A + min(m0 + r32, g.M - 1);
   const float* pb = g.B + min(n0 + r32, g.N - 1);
@@ -369,7 +376,8 @@ bool gemm_direct(GemmArgs g, float* ws, hipStream_t st) {
     else launch_dk_g<1>(g, tnw, kw, st);
     return true;
   }
-  if (g.sam == 1 && g.sbn == 1 && g.K >= 256 &&
+  // (a device row count is read by this kernel only: such a call takes it at every K)
+  if (g.sam == 1 && g.sbn == 1 && (g.K >= 256 || g.kdev) &&
       ((g.M + 31) / 32) * ((g.N + 31) / 32) >= kt_min_tiles()) {
     int splits = gemm_direct_splits(g.M, g.N, g.K);
     if (splits > 1 && !ws) return false;

@@ -317,10 +317,8 @@ TIED_CE_FUSED = True  # False (tests): logits GEMM + masked CE forward / backwar
 
 
 def tied_ce_supported(h, W, K, bias=None):
-    """Fused for both priors: at the LF prior's 6144 tokens the kernel is slower alone (96
-    blocks, ~100 us against ~70 us for the unfused launches) but the joint step is 0.02 ms
-    faster with it (fewer launches and no logits round trip; tools/step_ab.py, same box:
-    3.915-3.928 vs 3.940-3.947 ms)."""
+    """Fused for both priors (on the masked tokens only: HF ~42 us, LF ~19 us per step against
+    ~175 / ~70 us for the unfused launches, profiles/tlce_rows_ab.txt)."""
     if not (h.is_cuda and h.dim() == 3 and h.shape[-1] == 128 and W.shape[1] == 128
             and K in (64, 128, 256, 512) and W.shape[0] >= K):
         return False
@@ -335,11 +333,15 @@ def tied_ce_supported(h, W, K, bias=None):
 
 class _TiedLogitsCE(torch.autograd.Function):
     """masked_cross_entropy(h @ W[:K]^T + bias[:, :K], target, keep) for a backward that starts
-    at this loss with root gradient `gscale` (MaskGIT.forward_backward): tvq_tied_logits_ce
-    computes the loss, the logits' gradient D and dh = D W[:K] in the forward, the logits never
-    reaching memory (bidirectional_transformer.py:186-191, maskgit.py:183-191).  The backward
-    adds the tied-table and bias gradients (D^T h, the batch column sums of D) and returns dh;
-    a root gradient other than `gscale` (not the forward_backward use) rescales them first."""
+    at this loss with root gradient `gscale` (MaskGIT.forward_backward), on the masked tokens
+    only: tvq_masked_rows lists them (by position, then sample; the count stays on the device)
+    and tvq_tied_logits_ce computes the loss, the logits' gradient D and a copy Hc of the h
+    rows, both compact (one row per listed token), and the dense dh = D W[:K] (zero on the kept
+    tokens) in the forward, the logits never reaching memory (bidirectional_transformer.py:
+    186-191, maskgit.py:183-191).  The backward adds the tied-table and bias gradients
+    (D^T Hc, the per-position column sums of D: tvq_tied_ce_grads, over the listed rows) and
+    returns dh; a root gradient other than `gscale` (not the forward_backward use) rescales
+    them first (whole buffers: the rows past the count are never read)."""
 
     @staticmethod
     def forward(ctx, h, W, bias, K, target, keep, gscale):
@@ -347,22 +349,26 @@ class _TiedLogitsCE(torch.autograd.Function):
         M = B * n
         h2 = h.reshape(M, D).contiguous()
         dev = h.device
+        rows = torch.empty(M, device=dev, dtype=torch.int32)
+        pos_off = torch.empty(n + 1, device=dev, dtype=torch.int32)
+        call("tvq_masked_rows", ptr(keep.reshape(-1).contiguous()), B, n, ptr(rows), ptr(pos_off),
+             stream_ptr())
         ws = torch.empty(value("tvq_tied_logits_ce_workspace", M, K), device=dev)
         dl = torch.empty((M, K), device=dev)
+        hc = torch.empty((M, D), device=dev)
         dh = torch.empty((M, D), device=dev)
         out = torch.empty(2, device=dev)
         call("tvq_tied_logits_ce", ptr(h2), M, D, ptr(W.contiguous()), K, ptr(bias), bias.shape[0],
-             bias.stride(0), ptr(target.reshape(-1).contiguous()),
-             ptr(keep.reshape(-1).contiguous()), ptr(gscale), ptr(dl), ptr(dh), ptr(out), ptr(ws),
-             stream_ptr())
-        ctx.save_for_backward(h2, dl, dh, gscale)
+             bias.stride(0), ptr(target.reshape(-1).contiguous()), ptr(rows), ptr(pos_off),
+             ptr(gscale), ptr(dl), ptr(hc), ptr(dh), ptr(out), ptr(ws), stream_ptr())
+        ctx.save_for_backward(hc, dl, dh, gscale, pos_off)
         ctx.W, ctx.bias = W, bias
         ctx.cfg = (B, n, D, K, tuple(bias.shape))
         return out[0]
 
     @staticmethod
     def backward(ctx, g):
-        h2, dl, dh, gscale = ctx.saved_tensors
+        hc, dl, dh, gscale, pos_off = ctx.saved_tensors
         B, n, D, K, bshape = ctx.cfg
         M = B * n
         if g.data_ptr() != gscale.data_ptr():  # another root gradient: D, dh scale by g / gscale
@@ -372,22 +378,26 @@ class _TiedLogitsCE(torch.autograd.Function):
             dl, dh = scale_by(dl, r), scale_by(dh, r)
         need = ctx.needs_input_grad
         dW = dbias = None
-        if need[1]:
-            sink = grad_sink(ctx.W)
-            if sink is not None:
-                with streams.offload(dl, h2):
-                    gemm(dl, 1, K, h2, D, 1, K, D, M, out=sink, ldc=D, accumulate=True)
-            else:
-                dW = torch.zeros_like(ctx.W)
-                gemm(dl, 1, K, h2, D, 1, K, D, M, out=dW, ldc=D)
-        if need[2]:
-            sink = grad_sink(ctx.bias)
-            if sink is not None:
-                with streams.offload(dl):
-                    batch_colsum(dl.view(B, n, K), sink, bshape[1], True)
-            else:
-                dbias = torch.zeros(bshape, device=g.device)
-                batch_colsum(dl.view(B, n, K), dbias, bshape[1], False)
+        w_sink = grad_sink(ctx.W) if need[1] else None
+        b_sink = grad_sink(ctx.bias) if need[2] else None
+
+        def grads(dw, dw_acc, db, db_acc):
+            wsz = value("tvq_tied_ce_grads_workspace", M, K) if dw is not None else 0
+            ws = torch.empty(wsz, device=dl.device) if wsz > 0 else None
+            call("tvq_tied_ce_grads", ptr(dl), ptr(hc), ptr(pos_off), M, K, n, ptr(dw), int(dw_acc),
+                 ptr(db), bshape[1], int(db_acc), ptr(ws), stream_ptr())
+
+        if w_sink is not None or b_sink is not None:
+            # into the flat gradient, on the aux stream of this stream (next to the
+            # embedding-lookup gradient of the tied table: their order is fixed)
+            with streams.offload(dl, hc, pos_off):
+                grads(w_sink, True, b_sink, True)
+        if need[1] and w_sink is None:
+            dW = torch.zeros_like(ctx.W)
+            grads(dW, False, None, False)
+        if need[2] and b_sink is None:
+            dbias = torch.zeros(bshape, device=g.device)
+            grads(None, False, dbias, False)
         return (dh.view(B, n, D) if need[0] else None), dW, dbias, None, None, None, None
 
 
