@@ -232,6 +232,12 @@ int tvq_conv_out_width(int64_t Win, int64_t KW, int64_t SW, int64_t transposed);
  * 0 forces the staged GEMMs (with the stride-2 kernels); < 0 only queries.  Default 3.
  * Returns the previous setting. */
 int tvq_conv_config(int64_t halo);
+/* Block cap of the stride-2 small-channel kernels (conv_s2f / conv_s2t): a launch of S
+ * (image, segment) stages runs min(S, cap) blocks, each walking a contiguous run of stages
+ * through a two-buffer LDS ring; cap >= S is the one-shot launch (one stage per block).
+ * The results do not depend on it, bit for bit.  0 = the production choice per kernel,
+ * > 0 fixes the cap (tests, A/B), < 0 only queries.  Returns the previous setting. */
+int tvq_conv_s2_cap(int64_t cap);
 
 /* Per-step weight-pack cache for the staged-GEMM convs (their weights are repacked to
  * [tap][c][n] on every call otherwise).  begin(id, arena, cap, stream) opens a scope: it

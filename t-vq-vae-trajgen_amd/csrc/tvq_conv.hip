@@ -113,6 +113,12 @@ extern "C" int tvq_conv_config(int64_t halo) {
   return prev;
 }
 
+extern "C" int tvq_conv_s2_cap(int64_t cap) {
+  const int prev = g_conv_cfg.s2_cap;
+  if (cap >= 0) g_conv_cfg.s2_cap = cap > (1 << 30) ? (1 << 30) : (int)cap;
+  return prev;
+}
+
 extern "C" int tvq_conv_out_width(int64_t Win, int64_t KW, int64_t SW, int64_t transposed) {
   const int64_t PW = (KW - 1) / 2;
   return (int)(transposed ? (Win - 1) * SW - 2 * PW + KW : (Win + 2 * PW - KW) / SW + 1);

@@ -109,8 +109,8 @@ struct Epi {
   float bn_eps;
   int gelu;  // GELU (erf form) on conv + bias before the BN (Upscale: Conv1d -> GELU -> BN)
   // training BatchNorm statistics of the stored output (the stride-2 kernels' STATS form,
-  // tvq_conv2d_fwd_bnstats): per-block (sum, sum of squares) in fp64 at
-  // bn_part[(n * gridDim.x + blockIdx.x) * 2 + k]; null: off
+  // tvq_conv2d_fwd_bnstats): per-stage (sum, sum of squares) in fp64 at
+  // bn_part[(n * stages + stage) * 2 + k], stage = (image, segment); null: off
   double* bn_part;
 };
 
@@ -355,6 +355,7 @@ struct ConvConfig {
   int s2 = 1;     // conv_s2f / conv_s2t enabled (bit 512 turns them off)
   int ws2 = 1;    // conv_wgrad_s2_kernel enabled (bit 1024 turns it off)
   int n16 = 1;    // conv_n16_kernel enabled (bit 2048 turns it off)
+  int s2_cap = 0;  // conv_s2f / conv_s2t block cap (tvq_conv_s2_cap): 0 = the per-kernel default
 };
 const ConvConfig& conv_config();
 
@@ -367,7 +368,7 @@ const float* pack_weight(const float* wt, ConvGeom& g, int KK, float* ws, hipStr
 
 // tvq_conv_s2.hip
 int s2_kind(int mode, const ConvGeom& g);  // 0 none, 1 F, 2 T (Hout 3), 3 T (Hout 5)
-int64_t s2_blocks(const ConvGeom& g);      // grid size = per-channel partials of the STATS form
+int64_t s2_blocks(const ConvGeom& g);      // stages = per-channel partials of the STATS form
 void launch_s2(int k2, bool repl, const float* in, const float* wt, float* out, const ConvGeom& g,
                const Epi& e, hipStream_t st);
 bool s2_fold_fits(const ConvGeom& g);

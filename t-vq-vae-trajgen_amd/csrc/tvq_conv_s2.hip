@@ -10,24 +10,56 @@ namespace tvq {
 // EncBlock convs (F, replicate padding), the decoders' ConvTranspose tails (T) and the data
 // gradients of both (T into the replicate canvas / F).  The staged GEMMs above ran them at
 // 0.02-0.1 of peak: 9 K-steps of 16 with a branchy per-element gather and two barriers
-// each.  Here a block owns one image's 64-wide output segment on every output row: the input
-// rows it reads (C x rows x the segment's columns) are staged in LDS once, zero / replicate
-// padding applied while staging, and each wave runs its 16-position tiles as 16x16x4 MFMA
-// chains (rows = output channels, weights held in registers; columns = positions, read from
-// the staged rows).  F: k = (c, kh) x kw on the lane groups, every tap of the window is a
+// each.  Here a stage is one image's 64-wide output segment on every output row: the three
+// input rows it reads (C x 3 x the segment's columns) are staged in LDS, column padding
+// applied while staging, and each wave runs its 16-position tiles as 16x16x4 MFMA chains
+// (rows = output channels, weights held in registers; columns = positions, read from the
+// staged rows).  F: k = (c, kh) x kw on the lane groups, every tap of the window is a
 // term.  T (stride-2 gather): the output parity fixes which two kw have an integer source,
 // so each wave takes one parity and its K is c x kh x {two kw} (half the taps, no zero terms).
+//
+// Only the rows that exist are staged.  The padding rows (hi = -1, 3 of F; -2, -1, 3, 4 of T)
+// are not loaded: a replicate tap reads the clamped row, a zero tap reads rows of zeros that
+// are written once per block, so every MFMA of every chain keeps its operands and its place.
+//
+// A block takes a contiguous run of stages (grid = min(stages, cap), tvq_conv_s2_cap).  The
+// rows go global -> LDS by global_load_lds (4-byte form: a 257-wide row is not 16-byte
+// aligned; one wave instruction fills 64 consecutive floats from 64 per-lane addresses, so
+// replicate padding is a clamped address and zero padding the address of a zero word), into
+// two LDS buffers: while stage s multiplies and stores, stage s + 1 lands in the other one.
+// No prefetched value lives in a register.  Order per stage: wait for the DMA, barrier,
+// issue the next stage's DMA, MFMA chains, epilogue.  The one-shot launch (cap >= stages) is
+// the same kernel with one buffer.
 constexpr int S2_SEG = 64;                 // output positions per segment
 constexpr int S2_XRF = 2 * S2_SEG + 2;     // F: staged columns (stride 2, 4 taps)
 constexpr int S2_XRT = S2_SEG / 2 + 4;     // T: staged columns (source offsets -2..2)
 
+extern __shared__ float s2_lds[];
+static __device__ float s2_zero_word[4];  // never written: the source of a zero-padded cell
+
+// one wave instruction: 64 floats from the lanes' `src` to dst_wave[0..63]
+__device__ __forceinline__ void s2_glds(const float* src, float* dst_wave) {
+  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
+                                   (__attribute__((address_space(3))) void*)dst_wave, 4, 0, 0);
+}
+// the block's DMA has landed and every wave is done with the buffer it will overwrite
+__device__ __forceinline__ void s2_ring_sync() {
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+}
+
+struct S2Run {
+  int nst, spr;  // stages of the launch, stages per block
+};
+
 // STATS epilogue of the stride-2 kernels (4 waves): lane (r16, g4) holds its positions' sums
 // of channels 4 g4 + r in s1 / s2 (fp64); the 16 lanes of a g4 group are combined by a fixed
-// xor tree, the 4 waves in wave order, and each channel's block partial is written for
-// bn_apply_part_kernel (tvq_norm.hip), which finishes the statistics in the consumer.
-// Replaces the BatchNorm's separate statistics pass over the conv output (bn_stats_partial).
+// xor tree, the 4 waves in wave order, and each channel's partial of stage `slot` (of nslots)
+// is written for bn_apply_part_kernel (tvq_norm.hip), which finishes the statistics in the
+// consumer.  Replaces the BatchNorm's separate statistics pass over the conv output.
 __device__ __forceinline__ void s2_bn_stats_block(double (&s1)[4], double (&s2)[4], int nbase,
-                                                  int N, double* __restrict__ part) {
+                                                  int N, double* __restrict__ part, int slot,
+                                                  int nslots) {
   __shared__ double red[4][16][2];
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
 #pragma unroll
@@ -48,23 +80,51 @@ __device__ __forceinline__ void s2_bn_stats_block(double (&s1)[4], double (&s2)[
   const int t = threadIdx.x;
   if (t < 2 * N) {
     const int n = t >> 1, k = t & 1;
-    part[((int64_t)n * gridDim.x + blockIdx.x) * 2 + k] =
+    part[((int64_t)n * nslots + slot) * 2 + k] =
         ((red[0][n][k] + red[1][n][k]) + red[2][n][k]) + red[3][n][k];
   }
 }
 
 // F: out[b,n,h,wo] = sum_{c,kh,kw} w(n,c,kh,kw) in[b,c,h+kh-1,2wo+kw-opw], H = 3
+// LDS: [buffer][row 0..2][c][S2_XRF] (each buffer padded to whole wave instructions), then
+// CS rows of zeros for the taps of a zero-padded row.
+template <int CS>
+struct S2F {
+  static constexpr int RW = CS * S2_XRF;             // one input row of every channel
+  static constexpr int XN = 3 * RW, XNP = (XN + 63) / 64 * 64;
+  static constexpr int XPER = (XNP + 255) / 256;
+  static int lds_bytes(bool repl, int nbuf) { return (nbuf * XNP + (repl ? 0 : RW)) * 4; }
+};
 template <bool REPL, int CS, bool POST = false, bool STATS = false>
 __global__ __launch_bounds__(256) void conv_s2f_kernel(const float* __restrict__ in,
                                                        const float* __restrict__ wt,
-                                                       float* __restrict__ out, ConvGeom g, Epi e) {
-  constexpr int NS = 3 * CS, RS = 5;  // K-steps (c, kh); staged rows hi = -1..3
-  constexpr int XN = CS * RS * S2_XRF, XPER = (XN + 255) / 256;
-  __shared__ float Xs[XN];
+                                                       float* __restrict__ out, ConvGeom g, Epi e,
+                                                       S2Run run) {
+  using L = S2F<CS>;
+  constexpr int NS = 3 * CS;  // K-steps (c, kh)
+  float* const Xs = s2_lds;
   const int tid = threadIdx.x, lane = tid & 63, r16 = lane & 15, g4 = lane >> 4;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int segs = (g.Wo + S2_SEG - 1) / S2_SEG;
-  const int b = blockIdx.x / segs, w0 = (blockIdx.x - b * segs) * S2_SEG;
+  const int s_begin = blockIdx.x * run.spr, s_end = min(run.nst, s_begin + run.spr);
+  float* const Zs = Xs + (run.spr > 1 ? 2 : 1) * L::XNP;  // rows of zeros (!REPL)
+  // stage st's rows into buf: cell i = (row r, channel c, column j)
+  auto stage = [&](int st, float* buf) {
+    const int b = st / segs, w0 = (st - b * segs) * S2_SEG;
+    const float* inb = in + (int64_t)b * g.C * 3 * g.Win;
+#pragma unroll
+    for (int u = 0; u < L::XPER; ++u) {
+      if (256 * u + 64 * wid >= L::XNP) break;  // wave-uniform
+      const int i = tid + 256 * u;
+      const int rc = i / S2_XRF, j = i - rc * S2_XRF, r = rc / CS, c = rc - r * CS;
+      int wi = 2 * w0 - g.opw + j;
+      bool ok = i < L::XN && c < g.C;
+      if (REPL) wi = wi < 0 ? 0 : (wi >= g.Win ? g.Win - 1 : wi);
+      else ok = ok && wi >= 0 && wi < g.Win;
+      s2_glds(ok ? inb + ((int64_t)c * 3 + r) * g.Win + wi : s2_zero_word, buf + 256 * u + 64 * wid);
+    }
+  };
+  stage(s_begin, Xs);  // first: the weight, bias and BN loads below ride along with it
   // weights of row n = r16, tap kw = g4, step s = (c, kh)
   float af[NS];
   const int nr = r16 < g.N ? r16 : 0;
@@ -74,75 +134,66 @@ __global__ __launch_bounds__(256) void conv_s2f_kernel(const float* __restrict__
     const int cc = c < g.C ? c : 0;
     af[s] = wt[nr * g.wsn + cc * g.wsc + (kh * 4 + g4) * g.wst];
   }
-  const float* inb = in + (int64_t)b * g.C * g.Hin * g.Win;
-  float xv[XPER];
-  uint64_t okm = 0;
-#pragma unroll
-  for (int u = 0; u < XPER; ++u) {
-    const int i = tid + 256 * u;
-    const int ck = i / S2_XRF, j = i - ck * S2_XRF, c = ck / RS, r = ck - RS * c;
-    int hi = r - 1, wi = 2 * w0 - g.opw + j;
-    bool ok = i < XN && c < g.C;
-    if (REPL) {
-      hi = hi < 0 ? 0 : (hi >= g.Hin ? g.Hin - 1 : hi);
-      wi = wi < 0 ? 0 : (wi >= g.Win ? g.Win - 1 : wi);
-    } else {
-      ok = ok && hi >= 0 && hi < g.Hin && wi >= 0 && wi < g.Win;
-    }
-    xv[u] = inb[ok ? ((int64_t)c * g.Hin + hi) * g.Win + wi : 0];
-    okm |= (uint64_t)(ok ? 1 : 0) << u;
-  }
-#pragma unroll
-  for (int u = 0; u < XPER; ++u) {
-    const int i = tid + 256 * u;
-    if (i < XN) Xs[i] = (okm >> u & 1) ? xv[u] : 0.f;
-  }
   float bv[1][4];
   const int nbase = 4 * g4;
   epi_load_bias<1>(bv, e.bias, nbase, g.N);
-  __syncthreads();
-  // 12 tiles (3 rows x 4 position groups of 16), 3 per wave
-  floatx4 acc[3];
-  const float* xb[3];
-#pragma unroll
-  for (int t = 0; t < 3; ++t) {
-    const int tile = wid * 3 + t, h = tile >> 2, p0 = (tile & 3) * 16;
-    xb[t] = Xs + h * S2_XRF + 2 * (p0 + r16) + g4;
-    acc[t] = floatx4{0.f, 0.f, 0.f, 0.f};
-  }
-#pragma unroll
-  for (int s = 0; s < NS; ++s) {
-    const int c = s / 3, kh = s - 3 * c, off = (c * RS + kh) * S2_XRF;
-#pragma unroll
-    for (int t = 0; t < 3; ++t) acc[t] = mfma16x16x4(af[s], xb[t][off], acc[t]);
-  }
   const uint64_t seed = e.drop_p > 0.f ? mix_seed(e.seed_ptr, e.offset) : 0ull;
   const int64_t hw = (int64_t)g.Hout * g.Wo;
   PostTile<1> pt;
   if constexpr (POST) epi_load_post<1>(pt, e, nbase, g.N);
-#pragma unroll
-  for (int t = 0; t < 3; ++t) {
-    const int tile = wid * 3 + t, h = tile >> 2;
-    const int wo = w0 + (tile & 3) * 16 + r16;
-    const bool pv = wo < g.Wo;
-    const floatx4 a[1] = {acc[t]};
-    epi_store<1, POST>(out, e, seed, bv, a, ((int64_t)b * g.N * g.Hout + h) * g.Wo + (pv ? wo : 0),
-                       hw, nbase, g.N, pv, false, &pt);
-  }
-  if constexpr (STATS) {  // (no dropout / residual on this path: the stored value is acc + b)
-    double s1[4] = {0.0, 0.0, 0.0, 0.0}, s2[4] = {0.0, 0.0, 0.0, 0.0};
+  if (!REPL)
+    for (int i = tid; i < L::RW; i += 256) Zs[i] = 0.f;
+  for (int st = s_begin; st < s_end; ++st) {
+    float* const cur = Xs + ((st - s_begin) & 1) * L::XNP;
+    s2_ring_sync();
+    if (st + 1 < s_end) stage(st + 1, Xs + ((st + 1 - s_begin) & 1) * L::XNP);
+    const int b = st / segs, w0 = (st - b * segs) * S2_SEG;
+    // 12 tiles (3 rows x 4 position groups of 16), 3 per wave; rb[t][kh]: the staged row of
+    // output row h under tap kh (h + kh - 1, clamped or the zeros) at this lane's column
+    floatx4 acc[3];
+    const float* rb[3][3];
 #pragma unroll
     for (int t = 0; t < 3; ++t) {
-      const int tile = wid * 3 + t;
-      if (w0 + (tile & 3) * 16 + r16 >= g.Wo) continue;
+      const int tile = wid * 3 + t, h = tile >> 2, p0 = (tile & 3) * 16;
+      const int col = 2 * (p0 + r16) + g4;
 #pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const double v = (double)(acc[t][r] + bv[0][r]);
-        s1[r] += v;
-        s2[r] += v * v;
+      for (int kh = 0; kh < 3; ++kh) {
+        const int hi = h + kh - 1;
+        if (REPL) rb[t][kh] = cur + (hi < 0 ? 0 : (hi > 2 ? 2 : hi)) * L::RW + col;
+        else rb[t][kh] = (hi >= 0 && hi <= 2 ? cur + hi * L::RW : Zs) + col;
       }
+      acc[t] = floatx4{0.f, 0.f, 0.f, 0.f};
     }
-    s2_bn_stats_block(s1, s2, nbase, g.N, e.bn_part);
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+      const int c = s / 3, kh = s - 3 * c;
+#pragma unroll
+      for (int t = 0; t < 3; ++t) acc[t] = mfma16x16x4(af[s], rb[t][kh][c * S2_XRF], acc[t]);
+    }
+#pragma unroll
+    for (int t = 0; t < 3; ++t) {
+      const int tile = wid * 3 + t, h = tile >> 2;
+      const int wo = w0 + (tile & 3) * 16 + r16;
+      const bool pv = wo < g.Wo;
+      const floatx4 a[1] = {acc[t]};
+      epi_store<1, POST>(out, e, seed, bv, a, ((int64_t)b * g.N * g.Hout + h) * g.Wo + (pv ? wo : 0),
+                         hw, nbase, g.N, pv, false, &pt);
+    }
+    if constexpr (STATS) {  // (no dropout / residual on this path: the stored value is acc + b)
+      double s1[4] = {0.0, 0.0, 0.0, 0.0}, s2[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+      for (int t = 0; t < 3; ++t) {
+        const int tile = wid * 3 + t;
+        if (w0 + (tile & 3) * 16 + r16 >= g.Wo) continue;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const double v = (double)(acc[t][r] + bv[0][r]);
+          s1[r] += v;
+          s2[r] += v * v;
+        }
+      }
+      s2_bn_stats_block(s1, s2, nbase, g.N, e.bn_part, st, run.nst);
+    }
   }
 }
 
@@ -151,19 +202,49 @@ __global__ __launch_bounds__(256) void conv_s2f_kernel(const float* __restrict__
 // of a replicate-padded conv): the canvas (5 rows, Wo = Wx + 2 columns) is folded onto
 // out = dx (3 rows, Wx columns) in the epilogue -- rows 0+1, 2, 3+4; canvas columns 0 / Wx+1
 // onto dx columns 0 / Wx-1 through LDS -- instead of a canvas store and a fold launch.
+// The tap kh is the lane's (k = 4 s + g4), so the staged row must stay linear in h - kh:
+// LDS is [row][c][S2_XRT] with ZR rows of zeros before, between and after the buffers' three
+// real rows (ZR = 2 for HO = 5, 1 for HO = 3); neighbouring buffers share their zeros.
+template <int CS, int HO>
+struct S2T {
+  static constexpr int ZR = HO == 5 ? 2 : 1;
+  static constexpr int RW = CS * S2_XRT;
+  static constexpr int XN = 3 * RW, XNP = (XN + 63) / 64 * 64;  // the tail lands in zeros
+  static constexpr int XPER = (XNP + 255) / 256;
+  static constexpr int PER = (3 + ZR) * RW;  // buffer k's real rows start at ZR * RW + k * PER
+  static_assert(XNP - XN <= ZR * RW, "the DMA's tail must stay inside the zeros");
+  static int lds_bytes(int nbuf) { return (nbuf * PER + ZR * RW) * 4; }
+};
 template <int CS, int HO, bool FOLD = false, bool POST = false, bool STATS = false>
 __global__ __launch_bounds__(256) void conv_s2t_kernel(const float* __restrict__ in,
                                                        const float* __restrict__ wt,
-                                                       float* __restrict__ out, ConvGeom g, Epi e) {
-  constexpr int NS = 6 * CS / 4, RS = 7;  // K-steps; staged rows hi = -2..4
-  constexpr int XN = CS * RS * S2_XRT, XPER = (XN + 255) / 256;
-  __shared__ float Xs[XN];
+                                                       float* __restrict__ out, ConvGeom g, Epi e,
+                                                       S2Run run) {
+  using L = S2T<CS, HO>;
+  constexpr int NS = 6 * CS / 4;  // K-steps
+  float* const Xs = s2_lds;
   const int tid = threadIdx.x, lane = tid & 63, r16 = lane & 15, g4 = lane >> 4;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int par = wid & 1, mb = wid >> 1;  // this wave's output parity and 16-column group
   const int segs = (g.Wo + S2_SEG - 1) / S2_SEG;
-  const int b = blockIdx.x / segs, w0 = (blockIdx.x - b * segs) * S2_SEG;
-  const int m0 = w0 >> 1;  // staged column j <-> source column m0 - 2 + j
+  const int s_begin = blockIdx.x * run.spr, s_end = min(run.nst, s_begin + run.spr);
+  const int nbuf = run.spr > 1 ? 2 : 1;
+  // stage st's rows into buf (its first real row): cell i = (row r, channel c, column j),
+  // staged column j <-> source column m0 - 2 + j
+  auto stage = [&](int st, float* buf) {
+    const int b = st / segs, m0 = ((st - b * segs) * S2_SEG) >> 1;
+    const float* inb = in + (int64_t)b * g.C * 3 * g.Win;
+#pragma unroll
+    for (int u = 0; u < L::XPER; ++u) {
+      if (256 * u + 64 * wid >= L::XNP) break;  // wave-uniform
+      const int i = tid + 256 * u;
+      const int rc = i / S2_XRT, j = i - rc * S2_XRT, r = rc / CS, c = rc - r * CS;
+      const int wi = m0 - 2 + j;
+      const bool ok = i < L::XN && c < g.C && wi >= 0 && wi < g.Win;
+      s2_glds(ok ? inb + ((int64_t)c * 3 + r) * g.Win + wi : s2_zero_word, buf + 256 * u + 64 * wid);
+    }
+  };
+  stage(s_begin, Xs + L::ZR * L::RW);
   // step s, lane group g4: k = 4s + g4 = (c, kh, e), kw = q + 2e with q = (par + opw) & 1
   float af[NS];
   int soff[NS];
@@ -173,90 +254,80 @@ __global__ __launch_bounds__(256) void conv_s2t_kernel(const float* __restrict__
     const int k = 4 * s + g4, c = k / 6, rem = k - 6 * c, kh = rem >> 1, kw = q + 2 * (rem & 1);
     const int cc = c < g.C ? c : 0;
     af[s] = wt[nr * g.wsn + cc * g.wsc + (kh * 4 + kw) * g.wst];
-    soff[s] = (c * RS - kh) * S2_XRT + ((par + g.opw - kw) >> 1);
-  }
-  const float* inb = in + (int64_t)b * g.C * g.Hin * g.Win;
-  float xv[XPER];
-  uint32_t okm = 0;
-  static_assert(XPER <= 32, "staging mask");
-#pragma unroll
-  for (int u = 0; u < XPER; ++u) {
-    const int i = tid + 256 * u;
-    const int ck = i / S2_XRT, j = i - ck * S2_XRT, c = ck / RS, r = ck - RS * c;
-    const int hi = r - 2, wi = m0 - 2 + j;
-    const bool ok = i < XN && c < g.C && hi >= 0 && hi < g.Hin && wi >= 0 && wi < g.Win;
-    xv[u] = inb[ok ? ((int64_t)c * g.Hin + hi) * g.Win + wi : 0];
-    okm |= (uint32_t)(ok ? 1 : 0) << u;
-  }
-#pragma unroll
-  for (int u = 0; u < XPER; ++u) {
-    const int i = tid + 256 * u;
-    if (i < XN) Xs[i] = (okm >> u & 1) ? xv[u] : 0.f;
+    soff[s] = (c - kh * CS) * S2_XRT + ((par + g.opw - kw) >> 1);
   }
   float bv[1][4];
   const int nbase = 4 * g4;
   epi_load_bias<1>(bv, e.bias, nbase, g.N);
-  __syncthreads();
-  floatx4 acc[HO];
-  const float* xb = Xs + (g.oph + 2) * S2_XRT + mb * 16 + r16 + 2;
-#pragma unroll
-  for (int h = 0; h < HO; ++h) acc[h] = floatx4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int s = 0; s < NS; ++s)
-#pragma unroll
-    for (int h = 0; h < HO; ++h) acc[h] = mfma16x16x4(af[s], xb[h * S2_XRT + soff[s]], acc[h]);
-  const int wo = w0 + 2 * (mb * 16 + r16) + par;
-  if constexpr (FOLD) {
-    static_assert(HO == 5, "fold: replicate canvas");
-    __shared__ floatx4 ex[2][3][4];
-    const int Wx = g.Wo - 2;
-    floatx4 y[3] = {acc[0] + acc[1], acc[2], acc[3] + acc[4]};
-    if (wo == 0 || wo == Wx + 1) {
-#pragma unroll
-      for (int h = 0; h < 3; ++h) ex[wo == 0 ? 0 : 1][h][g4] = y[h];
-    }
-    __syncthreads();
-    if (wo == 1) {
-#pragma unroll
-      for (int h = 0; h < 3; ++h) y[h] = ex[0][h][g4] + y[h];
-    } else if (wo == Wx) {
-#pragma unroll
-      for (int h = 0; h < 3; ++h) y[h] = y[h] + ex[1][h][g4];
-    }
-    const bool pv = wo >= 1 && wo <= Wx;
-#pragma unroll
-    for (int h = 0; h < 3; ++h)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int n = nbase + r;
-        if (pv && n < g.N) out[(((int64_t)b * g.N + n) * 3 + h) * Wx + wo - 1] = y[h][r];
-      }
-    return;
-  }
   const uint64_t seed = e.drop_p > 0.f ? mix_seed(e.seed_ptr, e.offset) : 0ull;
   const int64_t hw = (int64_t)g.Hout * g.Wo;
-  const bool pv = wo < g.Wo;
   PostTile<1> pt;
   if constexpr (POST) epi_load_post<1>(pt, e, nbase, g.N);
+  for (int i = tid; i < nbuf * L::PER + L::ZR * L::RW; i += 256)
+    if ((i / L::RW) % (3 + L::ZR) < L::ZR) Xs[i] = 0.f;
+  for (int st = s_begin; st < s_end; ++st) {
+    float* const cur = Xs + ((st - s_begin) & 1) * L::PER;  // row hi = -ZR of this buffer
+    s2_ring_sync();
+    if (st + 1 < s_end) stage(st + 1, Xs + ((st + 1 - s_begin) & 1) * L::PER + L::ZR * L::RW);
+    const int b = st / segs, w0 = (st - b * segs) * S2_SEG;
+    floatx4 acc[HO];
+    const float* xb = cur + (g.oph + L::ZR) * L::RW + mb * 16 + r16 + 2;
 #pragma unroll
-  for (int h = 0; h < HO; ++h) {
-    const floatx4 a[1] = {acc[h]};
-    epi_store<1, POST>(out, e, seed, bv, a, ((int64_t)b * g.N * g.Hout + h) * g.Wo + (pv ? wo : 0),
-                       hw, nbase, g.N, pv, false, &pt);
-  }
-  if constexpr (STATS) {
-    double s1[4] = {0.0, 0.0, 0.0, 0.0}, s2[4] = {0.0, 0.0, 0.0, 0.0};
-    if (pv) {
+    for (int h = 0; h < HO; ++h) acc[h] = floatx4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-      for (int h = 0; h < HO; ++h)
+    for (int s = 0; s < NS; ++s)
+#pragma unroll
+      for (int h = 0; h < HO; ++h) acc[h] = mfma16x16x4(af[s], xb[h * L::RW + soff[s]], acc[h]);
+    const int wo = w0 + 2 * (mb * 16 + r16) + par;
+    if constexpr (FOLD) {
+      static_assert(HO == 5, "fold: replicate canvas");
+      __shared__ floatx4 ex[2][3][4];
+      const int Wx = g.Wo - 2;
+      floatx4 y[3] = {acc[0] + acc[1], acc[2], acc[3] + acc[4]};
+      if (wo == 0 || wo == Wx + 1) {
+#pragma unroll
+        for (int h = 0; h < 3; ++h) ex[wo == 0 ? 0 : 1][h][g4] = y[h];
+      }
+      __syncthreads();
+      if (wo == 1) {
+#pragma unroll
+        for (int h = 0; h < 3; ++h) y[h] = ex[0][h][g4] + y[h];
+      } else if (wo == Wx) {
+#pragma unroll
+        for (int h = 0; h < 3; ++h) y[h] = y[h] + ex[1][h][g4];
+      }
+      const bool pv = wo >= 1 && wo <= Wx;
+#pragma unroll
+      for (int h = 0; h < 3; ++h)
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          const double v = (double)(acc[h][r] + bv[0][r]);
-          s1[r] += v;
-          s2[r] += v * v;
+          const int n = nbase + r;
+          if (pv && n < g.N) out[(((int64_t)b * g.N + n) * 3 + h) * Wx + wo - 1] = y[h][r];
         }
+    } else {
+      const bool pv = wo < g.Wo;
+#pragma unroll
+      for (int h = 0; h < HO; ++h) {
+        const floatx4 a[1] = {acc[h]};
+        epi_store<1, POST>(out, e, seed, bv, a,
+                           ((int64_t)b * g.N * g.Hout + h) * g.Wo + (pv ? wo : 0), hw, nbase, g.N,
+                           pv, false, &pt);
+      }
+      if constexpr (STATS) {
+        double s1[4] = {0.0, 0.0, 0.0, 0.0}, s2[4] = {0.0, 0.0, 0.0, 0.0};
+        if (pv) {
+#pragma unroll
+          for (int h = 0; h < HO; ++h)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+              const double v = (double)(acc[h][r] + bv[0][r]);
+              s1[r] += v;
+              s2[r] += v * v;
+            }
+        }
+        s2_bn_stats_block(s1, s2, nbase, g.N, e.bn_part, st, run.nst);
+      }
     }
-    s2_bn_stats_block(s1, s2, nbase, g.N, e.bn_part);
   }
 }
 
@@ -273,34 +344,55 @@ int s2_kind(int mode, const ConvGeom& g) {
 
 int64_t s2_blocks(const ConvGeom& g) { return (int64_t)g.B * ((g.Wo + S2_SEG - 1) / S2_SEG); }
 
+// Blocks of a launch: min(stages, cap), the stages dealt in contiguous runs of `spr`.
+// S2_CAP_DEFAULT is the production cap (profiles/s2_ring_ab.txt).
+constexpr int S2_CAP_DEFAULT = 768;
+static S2Run s2_run(const ConvGeom& g, unsigned* grid) {
+  const int64_t nst = s2_blocks(g);
+  const int64_t cap = conv_config().s2_cap > 0 ? conv_config().s2_cap : S2_CAP_DEFAULT;
+  const int64_t blocks = nst < cap ? nst : cap;
+  S2Run r;
+  r.nst = (int)nst;
+  r.spr = (int)((nst + blocks - 1) / blocks);
+  *grid = (unsigned)((nst + r.spr - 1) / r.spr);
+  return r;
+}
+
 template <bool REPL>
 static void launch_s2_r(int kind, const float* in, const float* wt, float* out, const ConvGeom& g,
                         const Epi& e, hipStream_t st) {
-  const dim3 grid((unsigned)s2_blocks(g));
+  unsigned blocks;
+  const S2Run run = s2_run(g, &blocks);
+  const dim3 grid(blocks);
+  const int nbuf = run.spr > 1 ? 2 : 1;
   const int cs = (g.C + 3) / 4;
-  TVQ_PLAN("conv_s2%s cs%d hout%d%s", kind == 1 ? "f" : "t", 4 * cs, g.Hout,
-           e.bn_part ? " bnstats" : "");
-#define S2F(CSV)                                                                                \
-  do {                                                                                          \
-    if (e.bn_part)                                                                              \
-      hipLaunchKernelGGL((conv_s2f_kernel<REPL, CSV, false, true>), grid, dim3(256), 0, st, in,  \
-                         wt, out, g, e);                                                        \
-    else if (e.bn_rv)                                                                           \
-      hipLaunchKernelGGL((conv_s2f_kernel<REPL, CSV, true>), grid, dim3(256), 0, st, in, wt, out, \
-                         g, e);                                                                 \
-    else                                                                                        \
-      hipLaunchKernelGGL((conv_s2f_kernel<REPL, CSV>), grid, dim3(256), 0, st, in, wt, out, g, e); \
+  TVQ_PLAN("conv_s2%s cs%d hout%d%s blocks=%u per=%d", kind == 1 ? "f" : "t", 4 * cs, g.Hout,
+           e.bn_part ? " bnstats" : "", blocks, run.spr);
+#define S2F(CSV)                                                                                  \
+  do {                                                                                            \
+    const int lds = S2F<CSV>::lds_bytes(REPL, nbuf);                                              \
+    if (e.bn_part)                                                                                \
+      hipLaunchKernelGGL((conv_s2f_kernel<REPL, CSV, false, true>), grid, dim3(256), lds, st, in,  \
+                         wt, out, g, e, run);                                                     \
+    else if (e.bn_rv)                                                                             \
+      hipLaunchKernelGGL((conv_s2f_kernel<REPL, CSV, true>), grid, dim3(256), lds, st, in, wt,     \
+                         out, g, e, run);                                                         \
+    else                                                                                          \
+      hipLaunchKernelGGL((conv_s2f_kernel<REPL, CSV>), grid, dim3(256), lds, st, in, wt, out, g,   \
+                         e, run);                                                                 \
   } while (0)
-#define S2T(CSV, HOV)                                                                            \
-  do {                                                                                           \
-    if (e.bn_part)                                                                               \
-      hipLaunchKernelGGL((conv_s2t_kernel<CSV, HOV, false, false, true>), grid, dim3(256), 0, st, \
-                         in, wt, out, g, e);                                                     \
-    else if (e.bn_rv)                                                                            \
-      hipLaunchKernelGGL((conv_s2t_kernel<CSV, HOV, false, true>), grid, dim3(256), 0, st, in, wt, \
-                         out, g, e);                                                             \
-    else                                                                                         \
-      hipLaunchKernelGGL((conv_s2t_kernel<CSV, HOV>), grid, dim3(256), 0, st, in, wt, out, g, e); \
+#define S2T(CSV, HOV)                                                                              \
+  do {                                                                                             \
+    const int lds = S2T<CSV, HOV>::lds_bytes(nbuf);                                                \
+    if (e.bn_part)                                                                                 \
+      hipLaunchKernelGGL((conv_s2t_kernel<CSV, HOV, false, false, true>), grid, dim3(256), lds, st, \
+                         in, wt, out, g, e, run);                                                  \
+    else if (e.bn_rv)                                                                              \
+      hipLaunchKernelGGL((conv_s2t_kernel<CSV, HOV, false, true>), grid, dim3(256), lds, st, in,    \
+                         wt, out, g, e, run);                                                      \
+    else                                                                                           \
+      hipLaunchKernelGGL((conv_s2t_kernel<CSV, HOV>), grid, dim3(256), lds, st, in, wt, out, g, e,  \
+                         run);                                                                     \
   } while (0)
   if (kind == 1) {
     if (cs == 1) S2F(4); else if (cs == 2) S2F(8); else if (cs == 3) S2F(12); else S2F(16);
@@ -327,11 +419,16 @@ bool s2_fold_fits(const ConvGeom& g) {
 }
 void launch_s2_fold(const float* in, const float* wt, float* dx, const ConvGeom& g,
                     hipStream_t st) {
-  const dim3 grid((unsigned)s2_blocks(g));
+  unsigned blocks;
+  const S2Run run = s2_run(g, &blocks);
+  const dim3 grid(blocks);
+  const int nbuf = run.spr > 1 ? 2 : 1;
   const Epi e = {nullptr, nullptr, 0.f, 1.f, nullptr, 0};
   const int cs = (g.C + 3) / 4;
-  TVQ_PLAN("conv_s2t_fold cs%d", 4 * cs);
-#define S2T(CSV) hipLaunchKernelGGL((conv_s2t_kernel<CSV, 5, true>), grid, dim3(256), 0, st, in, wt, dx, g, e)
+  TVQ_PLAN("conv_s2t_fold cs%d blocks=%u per=%d", 4 * cs, blocks, run.spr);
+#define S2T(CSV)                                                                            \
+  hipLaunchKernelGGL((conv_s2t_kernel<CSV, 5, true>), grid, dim3(256),                      \
+                     (S2T<CSV, 5>::lds_bytes(nbuf)), st, in, wt, dx, g, e, run)
   if (cs == 1) S2T(4); else if (cs == 2) S2T(8); else if (cs == 3) S2T(12); else S2T(16);
 #undef S2T
 }
@@ -340,11 +437,12 @@ void launch_s2_fold(const float* in, const float* wt, float* dx, const ConvGeom&
 // both directions share (conv2d: G = dY, In = x;  ConvTranspose2d: G = x, In = dY):
 //   dW[n][c,kh,kw] = sum_{b,h,w} G[b,n,h,w] In[b,c,h+kh-1,2w+kw-opw],  db[n] = sum G
 // A block (8 waves) walks stages of one image's 64-wide G segment on all 3 rows: the G rows
-// (16 x 192) and the input rows they read (C x 5 x 130, padding applied while staging) go
-// through LDS with the next stage's loads in flight.  Wave w owns k' tiles w%4, w%4+4, ...
-// of the N x (12C+1) slab row for half of the stage's positions (w/4), so a k-step is one
-// G read shared by its tiles; each lane's column pointer is fixed once (window cell, a
-// ones plane for the bias column, a zeros plane past it).  The position halves are summed
+// (16 x 192) and the three input rows they read (C x 3 x 130, column padding applied while
+// staging) go through LDS with the next stage's loads in flight.  Wave w owns k' tiles w%4,
+// w%4+4, ... of the N x (12C+1) slab row for half of the stage's positions (w/4), so a k-step
+// is one G read shared by its tiles; each lane's column pointers are fixed once per G row the
+// wave meets (window cell of row h + kh - 1, clamped or the zeros plane for a padding row; a
+// ones plane for the bias column, the zeros plane past it).  The position halves are summed
 // in order at the end; blocks write slab rows (<= 256, one deferred ordered sum).
 constexpr int W2_T = 512, W2_GS = 3 * S2_SEG + 4, W2_KP = 2 * S2_XRF + 2 * S2_SEG + 8;
 struct W2Geom {
@@ -355,7 +453,7 @@ template <bool REPL, int CS>
 __global__ __launch_bounds__(W2_T) void conv_wgrad_s2_kernel(const float* __restrict__ G,
                                                             const float* __restrict__ X,
                                                             float* __restrict__ slab, W2Geom g) {
-  constexpr int RS = 5, XN = CS * RS * S2_XRF, XPER = (XN + W2_T - 1) / W2_T;
+  constexpr int RS = 3, XN = CS * RS * S2_XRF, XPER = (XN + W2_T - 1) / W2_T;
   constexpr int GN = 16 * 3 * S2_SEG, GPER = GN / W2_T;
   constexpr int KT = (12 * CS + 1 + 15) / 16, TPW = (KT + 3) / 4;
   constexpr int RED = 4 * TPW * 256;
@@ -369,14 +467,26 @@ __global__ __launch_bounds__(W2_T) void conv_wgrad_s2_kernel(const float* __rest
   const int nst = g.B * g.segs, z = blockIdx.x;
   const int s_begin = z * g.spr, s_end = min(nst, s_begin + g.spr);
   for (int i = tid; i < 2 * W2_KP; i += W2_T) K1[i] = i < W2_KP ? 1.f : 0.f;
-  // this lane's column pointer per tile (position offsets added per k-step)
-  const float* bp[TPW];
+  // This half's 24 k-steps are positions p = 96 ph + 4 i + g4 (row p / 64, column p % 64):
+  // steps 0-7 lie on G row ph, 8-15 on row 2 ph, 16-23 on row ph + 1.  A lane's column
+  // pointer per tile and row group, the group's first column folded in so that step i reads
+  // at 8 i (two input columns per position).
+  const float* bp[3][TPW];
 #pragma unroll
   for (int t = 0; t < TPW; ++t) {
     const int kc = (tg + 4 * t) * 16 + r16;
     const int k = kc < g.Kred ? kc : 0, c = k / 12, rem = k - 12 * c, kh = rem >> 2;
-    bp[t] = (kc < g.Kred ? Xs + (c * RS + kh) * S2_XRF + (rem & 3)
-                         : (kc == g.Kred && g.kcols > g.Kred ? K1 : K1 + W2_KP)) + 2 * g4;
+    const float* plane = (kc == g.Kred && g.kcols > g.Kred ? K1 : K1 + W2_KP) + 2 * g4;
+    auto row = [&](int h) -> const float* {
+      if (kc >= g.Kred) return plane;
+      int hi = h + kh - 1;
+      if (REPL) hi = hi < 0 ? 0 : (hi > 2 ? 2 : hi);
+      else if (hi < 0 || hi > 2) return K1 + W2_KP + 2 * g4;
+      return Xs + (c * RS + hi) * S2_XRF + (rem & 3) + 2 * g4;
+    };
+    bp[0][t] = row(ph) + 64 * ph;
+    bp[1][t] = row(2 * ph) - 64 * ph;
+    bp[2][t] = row(ph + 1) + 64 * ph - 128;
   }
   const float* ap = Gs + r16 * W2_GS + g4;
   float xv[XPER], gv[GPER];
@@ -387,15 +497,11 @@ __global__ __launch_bounds__(W2_T) void conv_wgrad_s2_kernel(const float* __rest
 #pragma unroll
     for (int u = 0; u < XPER; ++u) {
       const int i = tid + W2_T * u;
-      const int ck = i / S2_XRF, j = i - ck * S2_XRF, c = ck / RS, r = ck - RS * c;
-      int hi = r - 1, wi = 2 * w0 - g.opw + j;
+      const int ck = i / S2_XRF, j = i - ck * S2_XRF, c = ck / RS, hi = ck - RS * c;
+      int wi = 2 * w0 - g.opw + j;
       bool ok = i < XN && c < g.C;
-      if (REPL) {
-        hi = hi < 0 ? 0 : (hi > 2 ? 2 : hi);
-        wi = wi < 0 ? 0 : (wi >= g.Win ? g.Win - 1 : wi);
-      } else {
-        ok = ok && hi >= 0 && hi < 3 && wi >= 0 && wi < g.Win;
-      }
+      if (REPL) wi = wi < 0 ? 0 : (wi >= g.Win ? g.Win - 1 : wi);
+      else ok = ok && wi >= 0 && wi < g.Win;
       xv[u] = xb[ok ? ((int64_t)c * 3 + hi) * g.Win + wi : 0];
       okm = u == 0 ? (ok ? 1u : 0u) : (okm | (ok ? 1u : 0u) << u);
     }
@@ -431,14 +537,11 @@ __global__ __launch_bounds__(W2_T) void conv_wgrad_s2_kernel(const float* __rest
     store();
     __syncthreads();
     if (s + 1 < s_end) load(s + 1);  // in flight during this stage's chains
-    // this half's 24 k-steps: positions p = 96 ph + 4 i + g4 (row p / 64, column p % 64)
 #pragma unroll
     for (int i = 0; i < 24; ++i) {
-      const int p0 = 96 * ph + 4 * i, h = p0 / S2_SEG, w = p0 - h * S2_SEG;
-      const float a = ap[p0];
-      const int off = h * S2_XRF + 2 * w;
+      const float a = ap[96 * ph + 4 * i];
 #pragma unroll
-      for (int t = 0; t < TPW; ++t) acc[t] = mfma16x16x4(a, bp[t][off], acc[t]);
+      for (int t = 0; t < TPW; ++t) acc[t] = mfma16x16x4(a, bp[i >> 3][t][8 * i], acc[t]);
     }
   }
   __syncthreads();
