@@ -1,8 +1,6 @@
 // MaskGIT bidirectional-transformer kernels (K11-K16 in SURVEY.md §2.2).
 //
-//  rmsnorm     x-transformers RMSNorm: F.normalize(x) * sqrt(D) * g
-//  layernorm   LayerNorm over the last dim (gamma [+ beta]), eps given
-//  (attention: tvq_attn.hip)
+//  (RMSNorm, LayerNorm: tvq_rownorm.hip; attention: tvq_attn.hip)
 //  embedding   table gather (+ dropout on non-mask tokens) and a deterministic
 //              per-row scatter-add backward (no float atomics)
 //  masked CE   cross_entropy over the masked positions (maskgit.py:183-191)
@@ -25,419 +23,6 @@ __device__ __forceinline__ float gelu_grad(float x) {
   const float cdf = 0.5f * (1.0f + erff(x * 0.70710678118654752440f));
   const float pdf = 0.39894228040143267794f * expf(-0.5f * x * x);
   return cdf + x * pdf;
-}
-
-// ------------------------------------------------------------------ RMSNorm
-// one wave per row
-__global__ void rmsnorm_fwd_kernel(const float* __restrict__ x, int64_t M, int D,
-                                   const float* __restrict__ g, float scale, float* __restrict__ y,
-                                   float* __restrict__ inv_norm) {
-  const int lane = threadIdx.x & 63;
-  const int64_t row = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-  if (row >= M) return;
-  const float* xr = x + row * D;
-  float s = 0.f;
-  for (int d = lane; d < D; d += 64) s += xr[d] * xr[d];
-  s = wave_sum(s);
-  const float inv = 1.0f / fmaxf(sqrtf(s), 1e-12f);
-  for (int d = lane; d < D; d += 64) y[row * D + d] = xr[d] * inv * scale * g[d];
-  if (lane == 0) inv_norm[row] = inv;
-}
-
-// Narrow rows (D = 4L, L in {8, 16, 32, 64} lanes): one float4 per lane, 64 / L rows per
-// wave, the row sum over its L lanes by xor shuffles.  The one-wave-per-row form above
-// left half to 7/8 of the lanes idle on the HF prior's D = 32 rows and issued one 4-B load
-// per element (42 us for 1024 x 97 rows while sampling, ~0.3 TB/s).
-template <int L>
-__device__ __forceinline__ float group_sum(float v) {
-#pragma unroll
-  for (int o = L / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-template <int L>
-__global__ __launch_bounds__(256) void rmsnorm_fwd_vec_kernel(const float4* __restrict__ x,
-                                                              int64_t M,
-                                                              const float4* __restrict__ g,
-                                                              float scale, float4* __restrict__ y,
-                                                              float* __restrict__ inv_norm) {
-  const int lane = threadIdx.x & 63, sub = lane % L;
-  const int64_t row = ((int64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * (64 / L) + lane / L;
-  const bool ok = row < M;
-  const float4 v = ok ? x[row * L + sub] : make_float4(0.f, 0.f, 0.f, 0.f);
-  const float4 gv = g[sub];
-  float s = v.x * v.x;
-  s = fmaf(v.y, v.y, s);
-  s = fmaf(v.z, v.z, s);
-  s = fmaf(v.w, v.w, s);
-  s = group_sum<L>(s);
-  const float inv = 1.0f / fmaxf(sqrtf(s), 1e-12f);
-  if (!ok) return;
-  y[row * L + sub] = make_float4(v.x * inv * scale * gv.x, v.y * inv * scale * gv.y,
-                                 v.z * inv * scale * gv.z, v.w * inv * scale * gv.w);
-  if (sub == 0) inv_norm[row] = inv;
-}
-
-template <int L>
-__global__ __launch_bounds__(256) void layernorm_fwd_vec_kernel(
-    const float4* __restrict__ x, int64_t M, const float* __restrict__ gamma,
-    const float* __restrict__ beta, float eps, float4* __restrict__ y, float* __restrict__ mean_out,
-    float* __restrict__ rstd_out) {
-  constexpr int D = 4 * L;
-  const int lane = threadIdx.x & 63, sub = lane % L;
-  const int64_t row = ((int64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * (64 / L) + lane / L;
-  const bool ok = row < M;
-  const float4 v = ok ? x[row * L + sub] : make_float4(0.f, 0.f, 0.f, 0.f);
-  const float mean = group_sum<L>((v.x + v.y) + (v.z + v.w)) / (float)D;
-  const float t0 = v.x - mean, t1 = v.y - mean, t2 = v.z - mean, t3 = v.w - mean;
-  float q = t0 * t0;
-  q = fmaf(t1, t1, q);
-  q = fmaf(t2, t2, q);
-  q = fmaf(t3, t3, q);
-  const float var = group_sum<L>(q) / (float)D;
-  const float rstd = 1.0f / sqrtf(var + eps);
-  if (!ok) return;
-  const int d = 4 * sub;
-  const float4 gm = gamma ? *reinterpret_cast<const float4*>(gamma + d) : make_float4(1.f, 1.f, 1.f, 1.f);
-  float4 o = make_float4(t0 * rstd * gm.x, t1 * rstd * gm.y, t2 * rstd * gm.z, t3 * rstd * gm.w);
-  if (beta) {
-    const float4 bt = *reinterpret_cast<const float4*>(beta + d);
-    o.x += bt.x; o.y += bt.y; o.z += bt.z; o.w += bt.w;
-  }
-  y[row * L + sub] = o;
-  if (sub == 0) {
-    mean_out[row] = mean;
-    rstd_out[row] = rstd;
-  }
-}
-
-static bool a16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
-// dx; and per-block partial dg (deterministic, reduced by colsum_kernel)
-__global__ void rmsnorm_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ x,
-                                   int64_t M, int D, const float* __restrict__ g, float scale,
-                                   const float* __restrict__ inv_norm,
-                                   const float* __restrict__ dres, float* __restrict__ dx,
-                                   float* __restrict__ dg_part, int rows_per_block) {
-  extern __shared__ float sh[];  // [waves][D] partial dg
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, nw = blockDim.x >> 6;
-  for (int d = threadIdx.x; d < nw * D; d += blockDim.x) sh[d] = 0.f;
-  __syncthreads();
-  const int64_t r0 = (int64_t)blockIdx.x * rows_per_block;
-  for (int64_t row = r0 + wid; row < min(M, r0 + rows_per_block); row += nw) {
-    const float* xr = x + row * D;
-    const float* gr = dy + row * D;
-    const float inv = inv_norm[row];
-    // y = x * inv * scale * g ; norm = 1/inv (assumes ||x|| > 1e-12)
-    float dot = 0.f;
-    for (int d = lane; d < D; d += 64) dot += gr[d] * g[d] * xr[d];
-    dot = wave_sum(dot);
-    const float c = dot * scale * inv * inv * inv;
-    for (int d = lane; d < D; d += 64) {
-      const float v = gr[d] * g[d] * scale * inv - xr[d] * c;
-      dx[row * D + d] = dres ? v + dres[row * D + d] : v;  // + the residual path's gradient
-      sh[wid * D + d] += gr[d] * xr[d] * inv * scale;
-    }
-  }
-  __syncthreads();
-  for (int d = threadIdx.x; d < D; d += blockDim.x) {
-    float s = 0.f;
-    for (int w = 0; w < nw; ++w) s += sh[w * D + d];
-    dg_part[(int64_t)blockIdx.x * D + d] = s;
-  }
-}
-
-// The same backward with each row held in registers (D <= 64 ND): a wave loads its next
-// row while it reduces and stores the current one (the loop above pays two dependent
-// load round trips per row).  Every sum has the loop above's order: bitwise equal.
-template <int ND>
-__global__ __launch_bounds__(256) void rmsnorm_bwd_reg_kernel(
-    const float* __restrict__ dy, const float* __restrict__ x, int64_t M, int D,
-    const float* __restrict__ g, float scale, const float* __restrict__ inv_norm,
-    const float* __restrict__ dres, float* __restrict__ dx, float* __restrict__ dg_part,
-    int rows_per_block) {
-  extern __shared__ float sh[];  // [waves][D] partial dg
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, nw = blockDim.x >> 6;
-  for (int d = threadIdx.x; d < nw * D; d += blockDim.x) sh[d] = 0.f;
-  float gv[ND];
-#pragma unroll
-  for (int j = 0; j < ND; ++j) gv[j] = lane + 64 * j < D ? g[lane + 64 * j] : 0.f;
-  __syncthreads();
-  const int64_t r0 = (int64_t)blockIdx.x * rows_per_block;
-  const int64_t r1 = min(M, r0 + rows_per_block);
-  float cx[ND], cg[ND], cr[ND], nx[ND], ng[ND], nr[ND];
-  float cinv = 0.f, ninv = 0.f;
-  auto load = [&](int64_t row, float(&xv)[ND], float(&gvv)[ND], float(&rv)[ND], float& inv) {
-    const int64_t rr = row < r1 ? row : r0;  // past the block's rows: a valid row, unused
-#pragma unroll
-    for (int j = 0; j < ND; ++j) {
-      const int d = lane + 64 * j;
-      const int64_t o = rr * D + (d < D ? d : 0);
-      xv[j] = x[o];
-      gvv[j] = dy[o];
-      rv[j] = dres ? dres[o] : 0.f;
-    }
-    inv = inv_norm[rr];
-  };
-  int64_t row = r0 + wid;
-  if (row < r1) load(row, cx, cg, cr, cinv);
-  for (; row < r1; row += nw) {
-    load(row + nw, nx, ng, nr, ninv);
-    float dot = 0.f;
-#pragma unroll
-    for (int j = 0; j < ND; ++j)
-      if (lane + 64 * j < D) dot += cg[j] * gv[j] * cx[j];
-    dot = wave_sum(dot);
-    const float c = dot * scale * cinv * cinv * cinv;
-#pragma unroll
-    for (int j = 0; j < ND; ++j) {
-      const int d = lane + 64 * j;
-      if (d < D) {
-        const float v = cg[j] * gv[j] * scale * cinv - cx[j] * c;
-        dx[row * D + d] = dres ? v + cr[j] : v;
-        sh[wid * D + d] += cg[j] * cx[j] * cinv * scale;
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < ND; ++j) {
-      cx[j] = nx[j];
-      cg[j] = ng[j];
-      cr[j] = nr[j];
-    }
-    cinv = ninv;
-  }
-  __syncthreads();
-  for (int d = threadIdx.x; d < D; d += blockDim.x) {
-    float s = 0.f;
-    for (int w = 0; w < nw; ++w) s += sh[w * D + d];
-    dg_part[(int64_t)blockIdx.x * D + d] = s;
-  }
-}
-
-// D <= 32 (the HF prior): each half-wave takes a row, so a wave runs two rows at a time
-// (the one-row form left half of every wave idle); per-half dg partials in LDS.
-__global__ __launch_bounds__(256) void rmsnorm_bwd_half_kernel(
-    const float* __restrict__ dy, const float* __restrict__ x, int64_t M, int D,
-    const float* __restrict__ g, float scale, const float* __restrict__ inv_norm,
-    const float* __restrict__ dres, float* __restrict__ dx, float* __restrict__ dg_part,
-    int rows_per_block) {
-  extern __shared__ float sh[];  // [2 * waves][D] partial dg
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, nw = blockDim.x >> 6;
-  const int hl = lane >> 5, d = lane & 31;
-  const int slot = 2 * wid + hl, nslot = 2 * nw;
-  for (int i = threadIdx.x; i < nslot * D; i += blockDim.x) sh[i] = 0.f;
-  const float gv = d < D ? g[d] : 0.f;
-  __syncthreads();
-  const int64_t r0 = (int64_t)blockIdx.x * rows_per_block;
-  const int64_t r1 = min(M, r0 + rows_per_block);
-  float cx, cg, cr, cinv, nx, ng, nr, ninv;
-  auto load = [&](int64_t row, float& xv, float& gg, float& rv, float& inv) {
-    const int64_t rr = row < r1 ? row : r0;
-    const int64_t o = rr * D + (d < D ? d : 0);
-    xv = x[o];
-    gg = dy[o];
-    rv = dres ? dres[o] : 0.f;
-    inv = inv_norm[rr];
-  };
-  int64_t row = r0 + slot;
-  load(row, cx, cg, cr, cinv);
-  for (; row - hl < r1; row += nslot) {  // both halves iterate together (wave-uniform trip)
-    load(row + nslot, nx, ng, nr, ninv);
-    const bool live = row < r1 && d < D;
-    float dot = live ? cg * gv * cx : 0.f;
-#pragma unroll
-    for (int o = 16; o > 0; o >>= 1) dot += __shfl_xor(dot, o, 64);
-    const float c = dot * scale * cinv * cinv * cinv;
-    if (live) {
-      const float v = cg * gv * scale * cinv - cx * c;
-      dx[row * D + d] = dres ? v + cr : v;
-      sh[slot * D + d] += cg * cx * cinv * scale;
-    }
-    cx = nx;
-    cg = ng;
-    cr = nr;
-    cinv = ninv;
-  }
-  __syncthreads();
-  for (int i = threadIdx.x; i < D; i += blockDim.x) {
-    float t = 0.f;
-    for (int w = 0; w < nslot; ++w) t += sh[w * D + i];
-    dg_part[(int64_t)blockIdx.x * D + i] = t;
-  }
-}
-
-// out[d] (+)= sum_p part[p][d]
-__global__ void colsum_kernel(const float* __restrict__ part, int P, int D, float* __restrict__ out,
-                              int accumulate) {
-  const int d = blockIdx.x * blockDim.x + threadIdx.x;
-  if (d >= D) return;
-  float s = 0.f;
-  for (int p = 0; p < P; ++p) s += part[(int64_t)p * D + d];
-  out[d] = accumulate ? out[d] + s : s;
-}
-
-// ---------------------------------------------------------------- LayerNorm
-__global__ void layernorm_fwd_kernel(const float* __restrict__ x, int64_t M, int D,
-                                     const float* __restrict__ gamma,
-                                     const float* __restrict__ beta, float eps,
-                                     float* __restrict__ y, float* __restrict__ mean_out,
-                                     float* __restrict__ rstd_out) {
-  const int lane = threadIdx.x & 63;
-  const int64_t row = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-  if (row >= M) return;
-  const float* xr = x + row * D;
-  float s = 0.f;
-  for (int d = lane; d < D; d += 64) s += xr[d];
-  const float mean = wave_sum(s) / (float)D;
-  float v = 0.f;
-  for (int d = lane; d < D; d += 64) {
-    const float t = xr[d] - mean;
-    v += t * t;
-  }
-  const float var = wave_sum(v) / (float)D;
-  const float rstd = 1.0f / sqrtf(var + eps);
-  for (int d = lane; d < D; d += 64) {
-    float t = (xr[d] - mean) * rstd * (gamma ? gamma[d] : 1.f);
-    if (beta) t += beta[d];
-    y[row * D + d] = t;
-  }
-  if (lane == 0) {
-    mean_out[row] = mean;
-    rstd_out[row] = rstd;
-  }
-}
-
-__global__ void layernorm_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ x,
-                                     int64_t M, int D, const float* __restrict__ gamma,
-                                     const float* __restrict__ mean, const float* __restrict__ rstd,
-                                     float* __restrict__ dx, float* __restrict__ part,
-                                     int rows_per_block) {
-  extern __shared__ float sh[];  // [waves][2][D]: dgamma, dbeta partials
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, nw = blockDim.x >> 6;
-  for (int d = threadIdx.x; d < nw * 2 * D; d += blockDim.x) sh[d] = 0.f;
-  __syncthreads();
-  const int64_t r0 = (int64_t)blockIdx.x * rows_per_block;
-  for (int64_t row = r0 + wid; row < min(M, r0 + rows_per_block); row += nw) {
-    const float* xr = x + row * D;
-    const float* gr = dy + row * D;
-    const float mu = mean[row], rs = rstd[row];
-    float s1 = 0.f, s2 = 0.f;
-    for (int d = lane; d < D; d += 64) {
-      const float xh = (xr[d] - mu) * rs;
-      const float gg = gr[d] * (gamma ? gamma[d] : 1.f);
-      s1 += gg;
-      s2 += gg * xh;
-      sh[(wid * 2) * D + d] += gr[d] * xh;
-      sh[(wid * 2 + 1) * D + d] += gr[d];
-    }
-    s1 = wave_sum(s1) / (float)D;
-    s2 = wave_sum(s2) / (float)D;
-    for (int d = lane; d < D; d += 64) {
-      const float xh = (xr[d] - mu) * rs;
-      const float gg = gr[d] * (gamma ? gamma[d] : 1.f);
-      dx[row * D + d] = rs * (gg - s1 - xh * s2);
-    }
-  }
-  __syncthreads();
-  for (int d = threadIdx.x; d < 2 * D; d += blockDim.x) {
-    const int k = d / D, dd = d - k * D;
-    float s = 0.f;
-    for (int w = 0; w < nw; ++w) s += sh[(w * 2 + k) * D + dd];
-    part[((int64_t)k * gridDim.x + blockIdx.x) * D + dd] = s;  // [gamma | beta][block][D]
-  }
-}
-
-// The same backward with each row in registers (D <= 64 ND) and the next row loading
-// while the current one reduces; the sums keep the loop above's order (bitwise equal).
-template <int ND>
-__global__ __launch_bounds__(256) void layernorm_bwd_reg_kernel(
-    const float* __restrict__ dy, const float* __restrict__ x, int64_t M, int D,
-    const float* __restrict__ gamma, const float* __restrict__ mean,
-    const float* __restrict__ rstd, float* __restrict__ dx, float* __restrict__ part,
-    int rows_per_block) {
-  extern __shared__ float sh[];  // [waves][2][D]: dgamma, dbeta partials
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, nw = blockDim.x >> 6;
-  for (int d = threadIdx.x; d < nw * 2 * D; d += blockDim.x) sh[d] = 0.f;
-  float gm[ND];
-#pragma unroll
-  for (int j = 0; j < ND; ++j) {
-    const int d = lane + 64 * j;
-    gm[j] = gamma && d < D ? gamma[d] : 1.f;
-  }
-  __syncthreads();
-  const int64_t r0 = (int64_t)blockIdx.x * rows_per_block;
-  const int64_t r1 = min(M, r0 + rows_per_block);
-  float cx[ND], cg[ND], nx[ND], ng[ND];
-  float cmu = 0.f, crs = 0.f, nmu = 0.f, nrs = 0.f;
-  auto load = [&](int64_t row, float(&xv)[ND], float(&gv)[ND], float& mu, float& rs) {
-    const int64_t rr = row < r1 ? row : r0;  // past the block's rows: a valid row, unused
-#pragma unroll
-    for (int j = 0; j < ND; ++j) {
-      const int d = lane + 64 * j;
-      const int64_t o = rr * D + (d < D ? d : 0);
-      xv[j] = x[o];
-      gv[j] = dy[o];
-    }
-    mu = mean[rr];
-    rs = rstd[rr];
-  };
-  int64_t row = r0 + wid;
-  if (row < r1) load(row, cx, cg, cmu, crs);
-  for (; row < r1; row += nw) {
-    load(row + nw, nx, ng, nmu, nrs);
-    float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-    for (int j = 0; j < ND; ++j) {
-      const int d = lane + 64 * j;
-      if (d < D) {
-        const float xh = (cx[j] - cmu) * crs;
-        const float gg = cg[j] * gm[j];
-        s1 += gg;
-        s2 += gg * xh;
-        sh[(wid * 2) * D + d] += cg[j] * xh;
-        sh[(wid * 2 + 1) * D + d] += cg[j];
-      }
-    }
-    s1 = wave_sum(s1) / (float)D;
-    s2 = wave_sum(s2) / (float)D;
-#pragma unroll
-    for (int j = 0; j < ND; ++j) {
-      const int d = lane + 64 * j;
-      if (d < D) {
-        const float xh = (cx[j] - cmu) * crs;
-        const float gg = cg[j] * gm[j];
-        dx[row * D + d] = crs * (gg - s1 - xh * s2);
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < ND; ++j) {
-      cx[j] = nx[j];
-      cg[j] = ng[j];
-    }
-    cmu = nmu;
-    crs = nrs;
-  }
-  __syncthreads();
-  for (int d = threadIdx.x; d < 2 * D; d += blockDim.x) {
-    const int k = d / D, dd = d - k * D;
-    float s = 0.f;
-    for (int w = 0; w < nw; ++w) s += sh[(w * 2 + k) * D + dd];
-    part[((int64_t)k * gridDim.x + blockIdx.x) * D + dd] = s;  // [gamma | beta][block][D]
-  }
-}
-
-// dgamma[d] (+)= sum_p ws[p][0][d], dbeta[d] (+)= sum_p ws[p][1][d]
-__global__ void ln_colsum2_kernel(const float* __restrict__ ws, int P, int D,
-                                  float* __restrict__ dgamma, float* __restrict__ dbeta,
-                                  int accumulate) {
-  const int e = blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= 2 * D) return;
-  const int k = e / D, d = e - k * D;
-  float* dst = k == 0 ? dgamma : dbeta;
-  if (!dst) return;
-  float s = 0.f;
-  for (int p = 0; p < P; ++p) s += ws[((int64_t)p * 2 + k) * D + d];
-  dst[d] = accumulate ? dst[d] + s : s;
 }
 
 // ---------------------------------------------------------------- embedding
@@ -613,12 +198,6 @@ static int grid_for(int64_t n, int cap = 8192) {
   int64_t b = (n + 255) / 256;
   if (b < 1) b = 1;
   return (int)(b < cap ? b : cap);
-}
-
-static int norm_rows_per_block(int64_t M) {
-  // ~256 blocks of rows for the deterministic partial-sum backward
-  int64_t r = (M + 255) / 256;
-  return (int)(r < 4 ? 4 : r);
 }
 
 
@@ -900,121 +479,6 @@ extern "C" int tvq_scale_by(const float* x, int64_t n, const float* s, float* y,
   hipLaunchKernelGGL(scale_by_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream,
                      (const float4*)x, n4, s, (float4*)y);
   return launch_status("tvq_scale_by");
-}
-
-extern "C" int tvq_rmsnorm_fwd(const float* x, int64_t M, int64_t D, const float* g, float scale,
-                               float* y, float* inv_norm, tvq_stream_t stream) {
-  TVQ_CHECK_ARG(x && g && y && inv_norm && M > 0 && D > 0, "tvq_rmsnorm_fwd: bad arguments");
-  if ((D == 32 || D == 64 || D == 128 || D == 256) && a16(x) && a16(g) && a16(y)) {
-    const int L = (int)(D / 4), rows = 4 * (64 / L);
-    const dim3 grid((unsigned)((M + rows - 1) / rows));
-    hipStream_t st = (hipStream_t)stream;
-    TVQ_PLAN("rmsnorm_fwd_vec D%lld", (long long)D);
-#define RN_(LV)                                                                               \
-  hipLaunchKernelGGL(rmsnorm_fwd_vec_kernel<LV>, grid, dim3(256), 0, st, (const float4*)x, M, \
-                     (const float4*)g, scale, (float4*)y, inv_norm)
-    if (L == 8) RN_(8); else if (L == 16) RN_(16); else if (L == 32) RN_(32); else RN_(64);
-#undef RN_
-    return launch_status("tvq_rmsnorm_fwd");
-  }
-  hipLaunchKernelGGL(rmsnorm_fwd_kernel, dim3((unsigned)((M + 3) / 4)), dim3(256), 0,
-                     (hipStream_t)stream, x, M, (int)D, g, scale, y, inv_norm);
-  return launch_status("tvq_rmsnorm_fwd");
-}
-
-extern "C" int64_t tvq_norm_bwd_workspace(int64_t M, int64_t D) {
-  const int rpb = norm_rows_per_block(M);
-  const int64_t nb = (M + rpb - 1) / rpb;
-  return nb * 2 * D + 2 * reduce_rows_scratch(nb, D);
-}
-
-extern "C" int tvq_rmsnorm_bwd(const float* dy, const float* x, int64_t M, int64_t D,
-                               const float* g, float scale, const float* inv_norm,
-                               const float* dres, float* dx, float* dg, int64_t accumulate,
-                               float* workspace, tvq_stream_t stream) {
-  TVQ_CHECK_ARG(dy && x && g && inv_norm && dx && dg && workspace, "tvq_rmsnorm_bwd: bad args");
-  const int rpb = norm_rows_per_block(M);
-  const int nb = (int)((M + rpb - 1) / rpb);
-  hipStream_t st = (hipStream_t)stream;
-  const size_t lds = 4 * D * sizeof(float);
-  if (D <= 32)
-    hipLaunchKernelGGL(rmsnorm_bwd_half_kernel, dim3(nb), dim3(256), 2 * lds, st, dy, x, M, (int)D,
-                       g, scale, inv_norm, dres, dx, workspace, rpb);
-  else if (D <= 64)
-    hipLaunchKernelGGL(rmsnorm_bwd_reg_kernel<1>, dim3(nb), dim3(256), lds, st, dy, x, M, (int)D, g,
-                       scale, inv_norm, dres, dx, workspace, rpb);
-  else if (D <= 128)
-    hipLaunchKernelGGL(rmsnorm_bwd_reg_kernel<2>, dim3(nb), dim3(256), lds, st, dy, x, M, (int)D, g,
-                       scale, inv_norm, dres, dx, workspace, rpb);
-  else if (D <= 256)
-    hipLaunchKernelGGL(rmsnorm_bwd_reg_kernel<4>, dim3(nb), dim3(256), lds, st, dy, x, M, (int)D, g,
-                       scale, inv_norm, dres, dx, workspace, rpb);
-  else
-    hipLaunchKernelGGL(rmsnorm_bwd_kernel, dim3(nb), dim3(256), lds, st, dy, x, M, (int)D, g, scale,
-                       inv_norm, dres, dx, workspace, rpb);
-  // the gain gradient: into the flat gradient (accumulate) it joins an open deferral scope
-  if (accumulate)
-    param_rows_finish(workspace, nb, D, dg, 1, workspace + (int64_t)nb * 2 * D, st);
-  else
-    reduce_rows(workspace, nb, D, D, dg, nullptr, 0, 0, workspace + (int64_t)nb * 2 * D, st);
-  return launch_status("tvq_rmsnorm_bwd");
-}
-
-extern "C" int tvq_layernorm_fwd(const float* x, int64_t M, int64_t D, const float* gamma,
-                                 const float* beta, float eps, float* y, float* mean, float* rstd,
-                                 tvq_stream_t stream) {
-  TVQ_CHECK_ARG(x && y && mean && rstd && M > 0 && D > 0, "tvq_layernorm_fwd: bad arguments");
-  if ((D == 32 || D == 64 || D == 128 || D == 256) && a16(x) && a16(y) && a16(gamma) &&
-      a16(beta)) {
-    const int L = (int)(D / 4), rows = 4 * (64 / L);
-    const dim3 grid((unsigned)((M + rows - 1) / rows));
-    hipStream_t st = (hipStream_t)stream;
-    TVQ_PLAN("layernorm_fwd_vec D%lld", (long long)D);
-#define LN_(LV)                                                                                   \
-  hipLaunchKernelGGL(layernorm_fwd_vec_kernel<LV>, grid, dim3(256), 0, st, (const float4*)x, M, \
-                     gamma, beta, eps, (float4*)y, mean, rstd)
-    if (L == 8) LN_(8); else if (L == 16) LN_(16); else if (L == 32) LN_(32); else LN_(64);
-#undef LN_
-    return launch_status("tvq_layernorm_fwd");
-  }
-  hipLaunchKernelGGL(layernorm_fwd_kernel, dim3((unsigned)((M + 3) / 4)), dim3(256), 0,
-                     (hipStream_t)stream, x, M, (int)D, gamma, beta, eps, y, mean, rstd);
-  return launch_status("tvq_layernorm_fwd");
-}
-
-extern "C" int tvq_layernorm_bwd(const float* dy, const float* x, int64_t M, int64_t D,
-                                 const float* gamma, const float* mean, const float* rstd,
-                                 float* dx, float* dgamma, float* dbeta, int64_t accumulate,
-                                 float* workspace, tvq_stream_t stream) {
-  TVQ_CHECK_ARG(dy && x && mean && rstd && dx && workspace, "tvq_layernorm_bwd: bad args");
-  const int rpb = norm_rows_per_block(M);
-  const int nb = (int)((M + rpb - 1) / rpb);
-  hipStream_t st = (hipStream_t)stream;
-  const size_t lds = 8 * D * sizeof(float);
-  if (D <= 64)
-    hipLaunchKernelGGL(layernorm_bwd_reg_kernel<1>, dim3(nb), dim3(256), lds, st, dy, x, M, (int)D,
-                       gamma, mean, rstd, dx, workspace, rpb);
-  else if (D <= 128)
-    hipLaunchKernelGGL(layernorm_bwd_reg_kernel<2>, dim3(nb), dim3(256), lds, st, dy, x, M, (int)D,
-                       gamma, mean, rstd, dx, workspace, rpb);
-  else if (D <= 256)
-    hipLaunchKernelGGL(layernorm_bwd_reg_kernel<4>, dim3(nb), dim3(256), lds, st, dy, x, M, (int)D,
-                       gamma, mean, rstd, dx, workspace, rpb);
-  else
-    hipLaunchKernelGGL(layernorm_bwd_kernel, dim3(nb), dim3(256), lds, st, dy, x, M, (int)D, gamma,
-                       mean, rstd, dx, workspace, rpb);
-  // workspace [gamma | beta][nb][D]: two slabs of contiguous rows; into the flat gradient
-  // (accumulate) they join an open deferral scope
-  float* rs = workspace + (int64_t)nb * 2 * D;
-  float* rs2 = rs + reduce_rows_scratch(nb, D);
-  if (accumulate) {
-    if (dgamma) param_rows_finish(workspace, nb, D, dgamma, 1, rs, st);
-    if (dbeta) param_rows_finish(workspace + (int64_t)nb * D, nb, D, dbeta, 1, rs2, st);
-  } else {
-    if (dgamma) reduce_rows(workspace, nb, D, D, dgamma, nullptr, 0, 0, rs, st);
-    if (dbeta) reduce_rows(workspace + (int64_t)nb * D, nb, D, D, dbeta, nullptr, 0, 0, rs2, st);
-  }
-  return launch_status("tvq_layernorm_bwd");
 }
 
 extern "C" int tvq_embedding_fwd(const int64_t* idx, int64_t M, int64_t D, const float* table,

@@ -17,32 +17,42 @@ def _rows(x):
 
 
 # ------------------------------------------------------------------ RMSNorm
+def _rmsnorm_fwd(ctx, x, g, scale):
+    x2, M, D = _rows(x.contiguous())
+    y = torch.empty_like(x2)
+    inv = torch.empty(M, device=x.device, dtype=torch.float32)
+    call("tvq_rmsnorm_fwd", ptr(x2), M, D, ptr(g), float(scale), ptr(y), ptr(inv), stream_ptr())
+    ctx.save_for_backward(x2, g, inv)
+    ctx.g_param = g
+    ctx.scale = scale
+    ctx.shape = x.shape
+    return y.reshape(x.shape)
+
+
+def _rmsnorm_bwd(ctx, gy, gr):
+    """(dx, dg, None) with gr, the residual path's gradient (or None), added into dx."""
+    x2, g, inv = ctx.saved_tensors
+    M, D = x2.shape
+    dy = gy.reshape(M, D).contiguous()
+    dres = gr.reshape(M, D).contiguous() if gr is not None else None
+    dx = torch.empty_like(x2)
+    sink = grad_sink(ctx.g_param)
+    dg = sink if sink is not None else torch.empty(D, device=x2.device)
+    ws = torch.empty(value("tvq_norm_bwd_workspace", M, D), device=x2.device)
+    call("tvq_rmsnorm_bwd", ptr(dy), ptr(x2), M, D, ptr(g), float(ctx.scale), ptr(inv),
+         ptr(dres), ptr(dx), ptr(dg), int(sink is not None), ptr(ws), stream_ptr())
+    _keep(ws)  # its reduction may be deferred (hip.conv.wgrad_deferred)
+    return dx.reshape(ctx.shape), (None if sink is not None else dg), None
+
+
 class _RMSNorm(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, g, scale):
-        x2, M, D = _rows(x.contiguous())
-        y = torch.empty_like(x2)
-        inv = torch.empty(M, device=x.device, dtype=torch.float32)
-        call("tvq_rmsnorm_fwd", ptr(x2), M, D, ptr(g), float(scale), ptr(y), ptr(inv), stream_ptr())
-        ctx.save_for_backward(x2, g, inv)
-        ctx.g_param = g
-        ctx.scale = scale
-        ctx.shape = x.shape
-        return y.reshape(x.shape)
+        return _rmsnorm_fwd(ctx, x, g, scale)
 
     @staticmethod
     def backward(ctx, gy):
-        x2, g, inv = ctx.saved_tensors
-        M, D = x2.shape
-        dy = gy.reshape(M, D).contiguous()
-        dx = torch.empty_like(x2)
-        sink = grad_sink(ctx.g_param)
-        dg = sink if sink is not None else torch.empty(D, device=x2.device)
-        ws = torch.empty(value("tvq_norm_bwd_workspace", M, D), device=x2.device)
-        call("tvq_rmsnorm_bwd", ptr(dy), ptr(x2), M, D, ptr(g), float(ctx.scale), ptr(inv), None,
-             ptr(dx), ptr(dg), int(sink is not None), ptr(ws), stream_ptr())
-        _keep(ws)  # its reduction may be deferred (hip.conv.wgrad_deferred)
-        return dx.reshape(ctx.shape), (None if sink is not None else dg), None
+        return _rmsnorm_bwd(ctx, gy, None)
 
 
 def rmsnorm(x, g):
@@ -58,32 +68,13 @@ class _RMSNormRes(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, g, scale):
-        x2, M, D = _rows(x.contiguous())
-        y = torch.empty_like(x2)
-        inv = torch.empty(M, device=x.device, dtype=torch.float32)
-        call("tvq_rmsnorm_fwd", ptr(x2), M, D, ptr(g), float(scale), ptr(y), ptr(inv), stream_ptr())
-        ctx.save_for_backward(x2, g, inv)
-        ctx.g_param = g
-        ctx.scale = scale
-        ctx.shape = x.shape
-        return y.reshape(x.shape), x.view_as(x)
+        return _rmsnorm_fwd(ctx, x, g, scale), x.view_as(x)
 
     @staticmethod
     def backward(ctx, gy, gr):
-        x2, g, inv = ctx.saved_tensors
-        M, D = x2.shape
-        dx = torch.empty_like(x2)
         if gy is None:  # the normalised output unused: only the residual path
             return gr, None, None
-        dy = gy.reshape(M, D).contiguous()
-        dres = gr.reshape(M, D).contiguous() if gr is not None else None
-        sink = grad_sink(ctx.g_param)
-        dg = sink if sink is not None else torch.empty(D, device=x2.device)
-        ws = torch.empty(value("tvq_norm_bwd_workspace", M, D), device=x2.device)
-        call("tvq_rmsnorm_bwd", ptr(dy), ptr(x2), M, D, ptr(g), float(ctx.scale), ptr(inv),
-             ptr(dres), ptr(dx), ptr(dg), int(sink is not None), ptr(ws), stream_ptr())
-        _keep(ws)
-        return dx.reshape(ctx.shape), (None if sink is not None else dg), None
+        return _rmsnorm_bwd(ctx, gy, gr)
 
 
 def rmsnorm_res(x, g):
