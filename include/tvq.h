@@ -794,6 +794,32 @@ int tvq_rocket_apply(const double* X, int64_t n, int64_t L, int64_t ldx, const d
 int tvq_fid_moments(const double* z, int64_t N, int64_t D, double* mu, double* cov,
                     tvq_stream_t stream);
 
+/* ---- TSGBench statistics (evaluation/stat_metrics.py:5-60 MDD / ACD / SD / KD;
+ * csrc/tvq_stat.hip).  All float64; per-block partials go to `workspace` (the matching
+ * *_workspace() count of doubles) and are added in a fixed order, so results are bitwise
+ * identical from run to run.
+ * tvq_stat_moments: out6 = {min, max, mean, m2, m3, m4} of x (n >= 1), mean = sum / n and
+ *   m_k = sum (x - mean)^k / n (biased) about the mean already computed, as scipy.stats'
+ *   _moment (skew = m3 / m2^1.5, kurtosis = m4 / m2^2 - 3).
+ * tvq_stat_kde: out[g] = 1 / (n s sqrt(2 pi)) sum_i exp(-(grid[g] / s - x[i] / s)^2 / 2),
+ *   scipy.stats.gaussian_kde's estimate for d = 1 with bandwidth s > 0 (whiten, then
+ *   subtract).
+ * tvq_stat_acf_mean: out[k] = (1 / N) sum_n sum_{t < L - k} x[n ld + t] x[n ld + t + k],
+ *   k = 0..L-1: the mean over the series of np.correlate(s, s, "full")[L - 1:] (raw lags, no
+ *   mean removal, no normalisation); ld >= L is the row stride in elements (channel 0 of a
+ *   (N, C, L) tensor: ld = C L).  1 <= L <= tvq_stat_acf_max_len() = 8192; a longer series
+ *   is refused before any launch. */
+int64_t tvq_stat_moments_workspace(int64_t n);
+int tvq_stat_moments(const double* x, int64_t n, double* out6, double* workspace,
+                     tvq_stream_t stream);
+int64_t tvq_stat_kde_workspace(int64_t n, int64_t G);
+int tvq_stat_kde(const double* x, int64_t n, const double* grid, int64_t G, double s, double* out,
+                 double* workspace, tvq_stream_t stream);
+int64_t tvq_stat_acf_max_len(void);
+int64_t tvq_stat_acf_workspace(int64_t N, int64_t L);
+int tvq_stat_acf_mean(const double* x, int64_t N, int64_t ld, int64_t L, double* out,
+                      double* workspace, tvq_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------
  * FidelityEnhancer / Unet1D eval forward (models/fidelity_enhancer.py:284-498, the
  * sampler's post-decode refinement, generation/sampler.py:156-169).  (B, C, L) fp32.

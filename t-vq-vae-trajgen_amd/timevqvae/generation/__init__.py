@@ -1,4 +1,5 @@
-"""Sampling from trained models (reference generation/): the sampling half of TrainedModelSampler."""
+"""Sampling from trained models (reference generation/): TrainedModelSampler, its sampling
+half and its ROCKET evaluation half."""
 from .sampler import TrainedModelSampler
 
 __all__ = ["TrainedModelSampler"]

@@ -1,18 +1,30 @@
-"""TrainedModelSampler, sampling half (reference generation/sampler.py:26-169).
+"""TrainedModelSampler (reference generation/sampler.py:26-368, without its plots).
 
 Same constructor and `sample(n_samples, kind, class_index)` contract: Stage2 (with its
 frozen Stage1) is loaded from the reference's checkpoints, the FidelityEnhancer from
 `stage3.ckpt`'s `fidelity_enhancer.*` entries, and sampling runs MaskGIT iterative
-decoding, LF/HF decoding and the FidelityEnhancer on the HIP path.  The evaluation half
-(FCN features, FID/IS, PCA/t-SNE plots; do_evaluate=True) is evaluation outside the hot
-path and raises here."""
-from typing import Union
+decoding, LF/HF decoding and the FidelityEnhancer on the HIP path.
 
+The evaluation half (sampler.py:110-138, 171-368; do_evaluate=True) is there for the ROCKET
+feature extractor: `rocket_kernels`, `ts_len`, `n_classes`, `z_train`, `z_test`, the feature
+loops `compute_z`, `compute_z_rec`, `compute_z_svq`, `compute_z_gen` (the reference's batch
+loop; ROCKET transform and float64 normalisation on the device), `fid_score` and
+`stat_metrics` (timevqvae.evaluation).  The supervised FCN extractor and `inception_score`
+need the pretrained FCN, which is out of scope, and raise NotImplementedError;
+PCA, t-SNE and the log_* plots are not reproduced."""
+from typing import Tuple, Union
+
+import numpy as np
 import torch
 import torch.nn as nn
 
+from ..evaluation.eval_utils import calculate_fid
+from ..evaluation.metrics import FCN_OUT_OF_SCOPE, batched, rocket_features
+from ..evaluation.rocket_functions import DeviceKernels, generate_kernels
+from ..evaluation.stat_metrics import stat_metrics_device
 from ..models import FidelityEnhancer
 from ..trainers import Stage2
+from ..utils import remove_outliers
 from ..utils.sample_utils import conditional_sample, unconditional_sample
 from ..utils.checkpoint import read_state_dict
 
@@ -27,11 +39,8 @@ class TrainedModelSampler(nn.Module):
         super().__init__()
         assert feature_extractor_type in ["supervised_fcn", "rocket"], \
             "unavailable feature extractor type."
-        if do_evaluate:
-            raise NotImplementedError(
-                "TrainedModelSampler(do_evaluate=True): the FCN/FID/IS/PCA evaluation half of "
-                "generation/sampler.py is outside the HIP hot path; pass do_evaluate=False "
-                "(ROCKET features: timevqvae.evaluation.apply_kernels)")
+        if do_evaluate and feature_extractor_type == "supervised_fcn":
+            raise NotImplementedError("TrainedModelSampler(do_evaluate=True): " + FCN_OUT_OF_SCOPE)
         self.device = torch.device(device) if device is not None else torch.device("cuda")
         self.config = config
         self.X_train, self.Y_train, self.X_test, self.Y_test = X_train, Y_train, X_test, Y_test
@@ -56,6 +65,13 @@ class TrainedModelSampler(nn.Module):
         else:
             self.fidelity_enhancer = nn.Identity()
         self.to(self.device)
+        if do_evaluate:
+            self.rocket_kernels = generate_kernels(input_length, num_kernels=rocket_num_kernels)
+            self._device_kernels = DeviceKernels(self.rocket_kernels, self.device)
+            self.ts_len = self.X_train.shape[-1]  # time series length
+            self.n_classes = len(np.unique(self.Y_train))
+            self.z_train = self.compute_z("train")
+            self.z_test = self.compute_z("test")
 
     @torch.no_grad()
     def sample(self, n_samples: int, kind: str, class_index: Union[int, None] = None):
@@ -72,3 +88,63 @@ class TrainedModelSampler(nn.Module):
             mini = x_new[start:start + self.batch_size]
             out.append(self.fidelity_enhancer(mini.to(self.device)).cpu())
         return (x_new_l, x_new_h, x_new), torch.cat(out)
+
+    # ---- evaluation half (do_evaluate=True, ROCKET features) ----------------------------
+    def _extract_feature_representations(self, x):
+        """x (b c l) numpy or tensor -> (b d) float64 numpy (sampler.py:185-189): channel 0,
+        ROCKET, L2-normalised rows in float64."""
+        if not hasattr(self, "_device_kernels"):
+            raise RuntimeError("TrainedModelSampler was built with do_evaluate=False")
+        return rocket_features(x, self._device_kernels, torch.float64)
+
+    def _set(self, kind: str):
+        assert kind in ["train", "test"]
+        return self.X_train if kind == "train" else self.X_test
+
+    def compute_z(self, kind: str) -> np.ndarray:
+        """Features of X_train / X_test (sampler.py:278-304)."""
+        return batched(self._extract_feature_representations, self._set(kind), self.batch_size)
+
+    @torch.no_grad()
+    def compute_z_rec(self, kind: str) -> np.ndarray:
+        """Features of the stage-1 reconstructions of X_train / X_test (sampler.py:194-227)."""
+        def one(x):
+            x = torch.as_tensor(x).float().to(self.device)
+            x_rec = self.stage1.forward(batch=(x, None), batch_idx=-1, return_x_rec=True)
+            return self._extract_feature_representations(x_rec)
+        return batched(one, self._set(kind), self.batch_size)
+
+    @torch.no_grad()
+    def compute_z_svq(self, kind: str):
+        """(features, X') of the stochastic variant X' of X_train / X_test: tokens drawn with
+        svq_temp = the FidelityEnhancer's tau, decoded (sampler.py:229-276)."""
+        xs_a = []
+
+        def one(x):
+            x = torch.as_tensor(x).float().to(self.device)
+            tau = self.fidelity_enhancer.tau.item()
+            _, s_a_l = self.maskgit.encode_to_z_q(x, self.stage1.encoder_l, self.stage1.vq_model_l,
+                                                  svq_temp=tau)
+            _, s_a_h = self.maskgit.encode_to_z_q(x, self.stage1.encoder_h, self.stage1.vq_model_h,
+                                                  svq_temp=tau)
+            x_a = (self.maskgit.decode_token_ind_to_timeseries(s_a_l, "lf")
+                   + self.maskgit.decode_token_ind_to_timeseries(s_a_h, "hf"))  # (b c l)
+            xs_a.append(x_a.cpu().numpy().astype(float))
+            return self._extract_feature_representations(x_a)
+        zs = batched(one, self._set(kind), self.batch_size)
+        return zs, np.concatenate(xs_a, axis=0)
+
+    def compute_z_gen(self, X_gen: torch.Tensor) -> np.ndarray:
+        """Features of generated samples (sampler.py:306-327)."""
+        return batched(self._extract_feature_representations, X_gen, self.batch_size)
+
+    def fid_score(self, z1: np.ndarray, z2: np.ndarray):
+        z1, z2 = remove_outliers(z1), remove_outliers(z2)
+        return calculate_fid(z1, z2, self.device)
+
+    def inception_score(self, X_gen):
+        raise NotImplementedError("TrainedModelSampler.inception_score: " + FCN_OUT_OF_SCOPE)
+
+    def stat_metrics(self, x_real, x_gen) -> Tuple[float, float, float, float]:
+        """(mdd, acd, sd, kd) of TSGBench (Ang et al., arXiv:2309.03755); x (batch c length)."""
+        return tuple(stat_metrics_device(x_real, x_gen, self.device)[:4])

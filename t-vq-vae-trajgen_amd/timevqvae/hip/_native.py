@@ -255,6 +255,14 @@ F64 = ctypes.c_double
 sig("tvq_minmax_fit_workspace", I64, restype=I64)
 sig("tvq_minmax_fit", P, I64, I64, F64, F64, P, P, P, P, P, P)
 sig("tvq_fid_moments", P, I64, I64, P, P, P)
+# --- TSGBench statistics (MDD / ACD / SD / KD) --------------------------------
+sig("tvq_stat_moments_workspace", I64, restype=I64)
+sig("tvq_stat_moments", P, I64, P, P, P)
+sig("tvq_stat_kde_workspace", I64, I64, restype=I64)
+sig("tvq_stat_kde", P, I64, P, I64, F64, P, P, P)
+sig("tvq_stat_acf_max_len", restype=I64)
+sig("tvq_stat_acf_workspace", I64, I64, restype=I64)
+sig("tvq_stat_acf_mean", P, I64, I64, I64, P, P, P)
 sig("tvq_minmax_transform", P, I64, I64, I64, P, P, P, P)
 sig("tvq_minmax_inverse", P, I64, I64, I64, P, P, P, P)
 sig("tvq_codebook_gather_nchw", P, I64, I64, I64, P, P, P)
