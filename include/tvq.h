@@ -820,6 +820,37 @@ int64_t tvq_stat_acf_workspace(int64_t N, int64_t L);
 int tvq_stat_acf_mean(const double* x, int64_t N, int64_t ld, int64_t L, double* out,
                       double* workspace, tvq_stream_t stream);
 
+/* ---- Trajectory distances of the flyability evaluation (evaluation/flyability_utils/
+ * trajectory_distances as flyability_eval.py:271-351 calls them; csrc/tvq_traj.hip).
+ * All float64, no atomics: a pair's row depends on that pair alone and is bitwise the same in
+ * any batch.  A ragged batch of P pairs: pts0 (sum n0, 2) and pts1 (sum n1, 2) row-major,
+ * off0 / off1 (P + 1 int64, element p = first point of pair p) on the device, and the same
+ * offsets once more on the host (host_off0 / host_off1): the lengths are checked and the LDS
+ * is sized from the host copy before anything is launched.  out is (P, 13) row-major with
+ * the columns in the order of the reference's results dict: SSPD e, SSPD s, DTW e, DTW s,
+ * Hausdorff e, Hausdorff s, LCSS e, LCSS s, ERP e, ERP s, EDR e, EDR s, discrete Frechet
+ * (e Euclidean, s spherical; the spherical functions read column 0 as lon and column 1 as
+ * lat, R = 6378137, haversine with atan2).  Each entry point writes its own columns only.
+ * tvq_traj_table_distances: columns 2, 3, 6..12, the nine recurrences over the
+ *   (n0 + 1) x (n1 + 1) table with the reference's borders (DTW / Frechet inf, ERP the total
+ *   gap distance to (g0, g1) in every border cell, EDR / LCSS zero).  eps is the threshold
+ *   of Euclidean LCSS and EDR (cost < eps matches), eps_lcss_spherical and eps_edr_spherical
+ *   those of the spherical two.  1 <= n0, n1.
+ * tvq_traj_segment_distances: columns 0, 1, 4, 5 from the per-point minima over the other
+ *   trajectory's segments (point_to_seg / point_to_path).  2 <= n0, n1.
+ * n0, n1 <= tvq_traj_max_len() = 4096 (the table kernel keeps 36 bytes of LDS per point of
+ * t1).  A pair outside these limits is refused before any launch; P = 0 is a no-op. */
+int64_t tvq_traj_max_len(void);
+int tvq_traj_table_distances(const double* pts0, const int64_t* off0, const double* pts1,
+                             const int64_t* off1, const int64_t* host_off0,
+                             const int64_t* host_off1, int64_t P, double g0, double g1,
+                             double eps, double eps_lcss_spherical, double eps_edr_spherical,
+                             double* out, tvq_stream_t stream);
+int tvq_traj_segment_distances(const double* pts0, const int64_t* off0, const double* pts1,
+                               const int64_t* off1, const int64_t* host_off0,
+                               const int64_t* host_off1, int64_t P, double* out,
+                               tvq_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------
  * FidelityEnhancer / Unet1D eval forward (models/fidelity_enhancer.py:284-498, the
  * sampler's post-decode refinement, generation/sampler.py:156-169).  (B, C, L) fp32.

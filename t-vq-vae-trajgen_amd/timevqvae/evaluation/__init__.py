@@ -2,9 +2,15 @@
 FID / IS (reference evaluation/eval_utils.py; the FID moments on the device), the TSGBench
 statistics MDD / ACD / SD / KD (reference evaluation/stat_metrics.py; KDE, autocorrelation
 and central moments on the device) and the `Metrics` class (reference evaluation/metrics.py)
-for the ROCKET extractor.  The supervised FCN feature extractor, and with it the Inception
-Score of a trained classifier, is out of scope."""
+for the ROCKET extractor, and the flyability evaluation's trajectory distances (reference
+evaluation/flyability_eval.py calculate_trajectory_distances and flyability_utils/
+trajectory_distances; every table on the device).  The supervised FCN feature extractor, and
+with it the Inception Score of a trained classifier, is out of scope, as are the flyability
+evaluation's simulation, filtering and plotting and the continuous Frechet distance
+(DESIGN.md)."""
 from .eval_utils import calculate_fid, calculate_inception_score, feature_moments
+from .flyability_eval import calculate_trajectory_distances
+from .flyability_utils import trajectory_distances_device
 from .metrics import Metrics
 from .rocket_functions import (DeviceKernels, apply_kernel, apply_kernels, apply_kernels_device,
                                generate_kernels)
@@ -14,6 +20,7 @@ from .stat_metrics import (StatMetrics, auto_correlation_difference, kurtosis_di
 
 __all__ = ["DeviceKernels", "Metrics", "StatMetrics", "apply_kernel", "apply_kernels",
            "apply_kernels_device", "auto_correlation_difference", "calculate_fid",
-           "calculate_inception_score", "feature_moments", "generate_kernels",
+           "calculate_inception_score", "calculate_trajectory_distances", "feature_moments",
+           "generate_kernels",
            "kurtosis_difference", "marginal_distribution_difference", "skewness_difference",
-           "stat_metrics_device"]
+           "stat_metrics_device", "trajectory_distances_device"]
