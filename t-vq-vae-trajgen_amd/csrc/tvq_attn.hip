@@ -243,7 +243,9 @@ __global__ __launch_bounds__(256) void attention_bwd_kernel(AttnBwdArgs ab) {
             pp = kp ? p * dscale : 0.f;
             d = kp ? d * dscale : 0.f;
           }
-          g = p * (d - Ds[ql]);
+          // one key: the softmax is constant and dS is exactly 0 (d and Ds are the same
+          // dot product rounded in two orders, so their difference is not)
+          g = S > 1 ? p * (d - Ds[ql]) : 0.f;
           p = pp;
         }
         pd[i] = p;
