@@ -228,7 +228,9 @@ int tvq_conv_out_width(int64_t Win, int64_t KW, int64_t SW, int64_t transposed);
  * block (default 12 waves), 128 = its 64-channel variant for narrow maps (default off),
  * 256 = no direct small transposed-gather kernel, 512 = no stride-2 small-channel conv
  * kernels (conv_s2f / conv_s2t), 1024 = no stride-2 small-channel weight-gradient kernel,
- * 2048 = no few-output wide-input kernel (conv_n16: 128 -> <= 16 channels on (B, 128, 3, 32));
+ * 2048 = no few-output wide-input kernel (conv_n16: 128 -> <= 16 channels on (B, 128, 3, 32)),
+ * 4096 = no stride-2 transposed-gather kernel for the 64 -> 32 and 32 -> 16 channel levels
+ * (conv_s2m_t: the ConvTranspose forward and the replicate conv's data gradient);
  * 0 forces the staged GEMMs (with the stride-2 kernels); < 0 only queries.  Default 3.
  * Returns the previous setting. */
 int tvq_conv_config(int64_t halo);

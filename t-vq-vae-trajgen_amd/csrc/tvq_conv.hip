@@ -60,6 +60,11 @@ static bool launch_conv(int mode, int kind, bool repl, int KK, const float* in, 
       launch_s2(k2, repl, in, wt, out, g, e, st);
       return e.bn_rv != nullptr;
     }
+    if (mode == GATHER_T && !repl && s2m_t_fits(g, e)) {
+      if (ws) wt = pack_weight(wt, g, KK, ws, st);
+      launch_s2m_t(false, in, wt, e.bias, out, g, st);
+      return false;
+    }
   }
   if (launch_small(mode, kind, repl, in, wt, out, g, e, st)) return false;
   if (ws && g_conv_cfg.n16 && n16_geom_ok(mode, kind, g)) {
@@ -98,7 +103,7 @@ extern "C" int tvq_conv_config(int64_t halo) {
   const int prev = c.halo | (c.t32 ? 0 : 8) | (c.t32_bk == 32 ? 16 : 0) |
                    (c.t32_bk == 16 ? 32 : 0) | (c.t32_nw == 4 ? 64 : 0) | (c.t32_n64 ? 128 : 0) |
                    (c.small ? 0 : 256) | (c.s2 ? 0 : 512) | (c.ws2 ? 0 : 1024) |
-                   (c.n16 ? 0 : 2048);
+                   (c.n16 ? 0 : 2048) | (c.s2m ? 0 : 4096);
   if (halo >= 0) {
     c.halo = (int)(halo & 7);
     c.t32 = (halo & 8) ? 0 : 1;
@@ -109,6 +114,7 @@ extern "C" int tvq_conv_config(int64_t halo) {
     c.s2 = (halo & 512) ? 0 : 1;
     c.ws2 = (halo & 1024) ? 0 : 1;
     c.n16 = (halo & 2048) ? 0 : 1;
+    c.s2m = (halo & 4096) ? 0 : 1;
   }
   return prev;
 }
@@ -337,6 +343,16 @@ extern "C" int tvq_conv2d_dgrad(const float* dy, int64_t B, int64_t Co, int64_t 
     launch_s2_fold(dy, w, dx, g, st);
     return launch_status("tvq_conv2d_dgrad(replicate, s2)");
   }
+  if (KH == 3 && KW == 4 && SW == 2 && s2m_fold_fits(g)) {
+    // packed [tap][c][n] behind the canvas's place, where the staged path puts it: the same
+    // pack-cache entry either way.  The canvas itself stays in LDS here, so its
+    // tvq_conv_workspace share (op 2) is unused by this launch; it is still sized, because the
+    // workspace is asked for by shape alone and bit 4096 sends the same shape to the staged path
+    const float* wp = w;
+    if (workspace) wp = pack_weight(w, g, (int)(KH * KW), workspace + canvas_floats(g), st);
+    launch_s2m_t(true, dy, wp, nullptr, dx, g, st);
+    return launch_status("tvq_conv2d_dgrad(replicate, s2m)");
+  }
   TVQ_CHECK_ARG(workspace, "tvq_conv2d_dgrad: replicate needs a workspace");
   float* canvas = workspace;
   float* rest = workspace + canvas_floats(g);
@@ -376,6 +392,8 @@ extern "C" int64_t tvq_conv_workspace(int64_t op, int64_t B, int64_t Ci, int64_t
     case 1: r = conv_gemm_ws(geom_convT_fwd(B, Ci, H, Wi, Co, KH, KW, SW), KK); break;
     case 2: {
       const ConvGeom g = geom_conv_dgrad(B, Ci, H, Wi, Co, KH, KW, SW, replicate);
+      // the canvas share is sized for every replicate shape, also where conv_s2t's / conv_s2m_t's
+      // fold form keeps the canvas in LDS: bit 512 / 4096 send the same shape to the staged path
       r = (replicate ? canvas_floats(g) : 0) + conv_gemm_ws(g, KK);
       break;
     }

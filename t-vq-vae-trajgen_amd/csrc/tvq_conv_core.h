@@ -21,6 +21,7 @@
 //   tvq_conv_d32.hip    conv_d32 (narrow maps, no LDS staging)
 //   tvq_conv_halo.hip   conv_halo / conv_small / conv_n16
 //   tvq_conv_s2.hip     conv_s2f / conv_s2t (+ fold), conv_wgrad_s2
+//   tvq_conv_s2m.hip    conv_s2m_t (+ fold): the same T gather at 32 / 64 reduction channels
 //   tvq_conv_wgrad.hip  the other weight gradients, their entry points, the deferred split
 //                       sums, tvq_channel_sum
 //   tvq_conv_pack.hip   weight packing and the pack cache
@@ -355,6 +356,7 @@ struct ConvConfig {
   int s2 = 1;     // conv_s2f / conv_s2t enabled (bit 512 turns them off)
   int ws2 = 1;    // conv_wgrad_s2_kernel enabled (bit 1024 turns it off)
   int n16 = 1;    // conv_n16_kernel enabled (bit 2048 turns it off)
+  int s2m = 1;    // conv_s2m_t enabled (bit 4096 turns it off)
   int s2_cap = 0;  // conv_s2f / conv_s2t block cap (tvq_conv_s2_cap): 0 = the per-kernel default
 };
 const ConvConfig& conv_config();
@@ -377,6 +379,14 @@ bool ws2_fits(int64_t C, int64_t H, int64_t N, int64_t KH, int64_t KW, int64_t S
 int64_t ws2_ws(int64_t B, int64_t C, int64_t Wo, int64_t N);
 int ws2_launch(const float* G, const float* X, float* slab, int B, int C, int N, int Win, int Wo,
                int kcols, bool repl, hipStream_t st);
+
+// tvq_conv_s2m.hip: the LF band's middle levels (32 / 64 reduction channels).  s2m_t_fits: the
+// Hout 3 T form with a bias-only epilogue; s2m_fold_fits: the replicate canvas geometry, folded
+// onto dx in the kernel
+bool s2m_t_fits(const ConvGeom& g, const Epi& e);
+bool s2m_fold_fits(const ConvGeom& g);
+void launch_s2m_t(bool fold, const float* in, const float* wt, const float* bias, float* out,
+                  const ConvGeom& g, hipStream_t st);
 
 // tvq_conv_halo.hip (*post: the epilogue applied e's eval BN / Snake)
 bool launch_small(int mode, int kind, bool repl, const float* in, const float* wt, float* out,
