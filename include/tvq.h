@@ -852,6 +852,29 @@ int tvq_traj_segment_distances(const double* pts0, const int64_t* off0, const do
                                const int64_t* off1, const int64_t* host_off0,
                                const int64_t* host_off1, int64_t P, double* out,
                                tvq_stream_t stream);
+/* The continuous Frechet distance (trajectory_distances/frechet.py, the 14th distance of
+ * flyability_eval.py:271-351; csrc/tvq_traj_frechet.hip): the same ragged batch, out (P,)
+ * float64.  Per pair the critical values (end_point and every cell's Lij / Bij above it) are
+ * written, sorted and made unique on the device, then one workgroup runs the reference's
+ * binary search, deciding each probe over the whole free-space diagram; the result is the
+ * last probed value (end_point when there is nothing to probe, e.g. a one-point side).
+ * 1 <= n0, n1 <= tvq_traj_max_len(), at most 65536 pairs a call.  The workspace holds two
+ * copies of every pair's value list (2 (n0 - 1)(n1 - 1) + 1 values rounded up to 4096, 8
+ * bytes each) plus 16 bytes a pair: tvq_traj_frechet_workspace returns the bytes (-1 with
+ * the error set for a refused length); a smaller workspace is refused before any launch.
+ * P = 0 is a no-op (0 bytes).
+ * tvq_traj_frechet_stages runs a subset for timing: stages is a mask of 1 (critical values),
+ * 2 (sort and unique) and 4 (search); a stage reads what the one before left in the
+ * workspace, so the masks are run in order on one workspace.  tvq_traj_frechet is mask 7. */
+int64_t tvq_traj_frechet_workspace(const int64_t* host_off0, const int64_t* host_off1, int64_t P);
+int tvq_traj_frechet(const double* pts0, const int64_t* off0, const double* pts1,
+                     const int64_t* off1, const int64_t* host_off0, const int64_t* host_off1,
+                     int64_t P, double* out, void* workspace, int64_t workspace_bytes,
+                     tvq_stream_t stream);
+int tvq_traj_frechet_stages(const double* pts0, const int64_t* off0, const double* pts1,
+                            const int64_t* off1, const int64_t* host_off0,
+                            const int64_t* host_off1, int64_t P, double* out, void* workspace,
+                            int64_t workspace_bytes, int stages, tvq_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
  * FidelityEnhancer / Unet1D eval forward (models/fidelity_enhancer.py:284-498, the

@@ -16,7 +16,12 @@ The semantics are the reference's, quirks included: the spherical functions read
 the longitude and column 1 as the latitude whatever the caller put there, every ERP border
 cell holds the total gap distance, EDR's borders are zero, `s_sspd` does not halve, and the
 thresholds are compared with `cost < eps`.  A pair's row does not depend on the batch it is
-in (bitwise).  The continuous `frechet` is not provided.  There is no CPU fallback."""
+in (bitwise).  There is no CPU fallback.
+
+The continuous `frechet` (the reference's 14th distance) is apart from the 13 COLUMNS:
+`frechet_device` scores a list of pairs with csrc/tvq_traj_frechet.hip (critical values,
+sort and unique, binary search with a free-space decision per probe, all on the device) and
+`frechet(P, Q)` is the reference's per-pair function."""
 import numpy as np
 import torch
 
@@ -175,3 +180,73 @@ def s_edr(t0, t1, eps):
 
 def discret_frechet(t0, t1):
     return _one("Discrete Frechet", "table", t0, t1)
+
+
+FRECHET_MAX_PAIRS = 65536  # pairs per tvq_traj_frechet call
+
+
+def _frechet_bytes(h0, h1, a, b):
+    """The workspace of pairs a..b-1, from the host offsets."""
+    return int(value("tvq_traj_frechet_workspace", h0[a:].ctypes.data, h1[a:].ctypes.data, b - a))
+
+
+def _frechet_chunks(h0, h1, budget):
+    """[(a, b)]: consecutive runs of pairs, each the longest whose workspace fits `budget`."""
+    P, chunks, a = h0.size - 1, [], 0
+    while a < P:
+        if _frechet_bytes(h0, h1, a, a + 1) > budget:
+            raise ValueError(
+                f"frechet: pair {a} ({h0[a + 1] - h0[a]} x {h1[a + 1] - h1[a]} points) needs a "
+                f"workspace of {_frechet_bytes(h0, h1, a, a + 1)} bytes, workspace_bytes is "
+                f"{budget}")
+        lo, hi = a + 1, min(P, a + FRECHET_MAX_PAIRS)  # the workspace grows with the run
+        while lo < hi:
+            mid = (lo + hi + 1) // 2
+            if _frechet_bytes(h0, h1, a, mid) <= budget:
+                lo = mid
+            else:
+                hi = mid - 1
+        chunks.append((a, lo))
+        a = lo
+    return chunks
+
+
+def frechet_device(gen, sim, device=None, workspace_bytes=1 << 30):
+    """(P,) float64 device tensor: the continuous Frechet distance of (gen[p], sim[p]), the
+    reference's trajectory_distances.frechet (csrc/tvq_traj_frechet.hip).
+
+    gen, sim: as for trajectory_distances_device; a one-point trajectory is accepted (the
+    result is the larger end-point distance).  The critical values of a pair, sorted on the
+    device, take 32 (n0 - 1)(n1 - 1) bytes of workspace: the batch runs in chunks of
+    consecutive pairs that fit `workspace_bytes`, and a single pair that does not is refused.
+    A pair's value does not depend on the batch or the chunking (bitwise)."""
+    gen, sim = list(gen), list(sim)
+    if len(gen) != len(sim):
+        raise ValueError(f"trajectory_distances: {len(gen)} generated and {len(sim)} simulated "
+                         f"trajectories")
+    t0s = [_as_tensor(a, "gen", k, 1) for k, a in enumerate(gen)]
+    t1s = [_as_tensor(a, "sim", k, 1) for k, a in enumerate(sim)]
+    chunks = _frechet_chunks(_offsets(t0s), _offsets(t1s), int(workspace_bytes))
+    if device is not None:
+        dev = torch.device(device)
+    else:
+        cuda = [t.device for t in t0s + t1s if t.is_cuda]
+        dev = cuda[0] if cuda else torch.device("cuda", torch.cuda.current_device())
+    P = len(t0s)
+    if P == 0:
+        return torch.empty((0,), dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        pts0, off0, pts1, off1, h0, h1 = _pack(t0s, t1s, dev)
+        out = torch.full((P,), float("nan"), dtype=torch.float64, device=dev)
+        need = max(_frechet_bytes(h0, h1, a, b) for a, b in chunks)
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        for a, b in chunks:  # one stream: a chunk reuses the workspace after the one before
+            call("tvq_traj_frechet", ptr(pts0), ptr(off0[a:]), ptr(pts1), ptr(off1[a:]),
+                 h0[a:].ctypes.data, h1[a:].ctypes.data, b - a, ptr(out[a:]), ptr(ws), need,
+                 stream_ptr())
+    return out
+
+
+def frechet(P, Q):
+    """The continuous Frechet distance of one pair, as the reference's frechet.frechet."""
+    return float(frechet_device([P], [Q])[0])

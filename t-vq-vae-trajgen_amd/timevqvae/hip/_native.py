@@ -267,6 +267,9 @@ sig("tvq_stat_acf_mean", P, I64, I64, I64, P, P, P)
 sig("tvq_traj_max_len", restype=I64)
 sig("tvq_traj_table_distances", P, P, P, P, P, P, I64, F64, F64, F64, F64, F64, P, P)
 sig("tvq_traj_segment_distances", P, P, P, P, P, P, I64, P, P)
+sig("tvq_traj_frechet_workspace", P, P, I64, restype=I64)
+sig("tvq_traj_frechet", P, P, P, P, P, P, I64, P, P, I64, P)
+sig("tvq_traj_frechet_stages", P, P, P, P, P, P, I64, P, P, I64, I32, P)
 sig("tvq_minmax_transform", P, I64, I64, I64, P, P, P, P)
 sig("tvq_minmax_inverse", P, I64, I64, I64, P, P, P, P)
 sig("tvq_codebook_gather_nchw", P, I64, I64, I64, P, P, P)

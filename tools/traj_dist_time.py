@@ -7,8 +7,15 @@ SSPD / Hausdorff) is timed with device events around its one launch on the packe
 `--runs` times (at least 20), median reported; the upload (packing on the host, one copy,
 widening on the device) and `trajectory_distances_device` end to end from the host arrays are
 timed with a host clock around a synchronise.  Cell rates are counted from the shapes
-(n0 n1 cells per pair and geometry; n0 (n1 - 1) + n1 (n0 - 1) point-segment pairs).  Writes one
-JSON (default profiles/traj_dist_time.json) and prints it.
+(n0 n1 cells per pair and geometry; n0 (n1 - 1) + n1 (n0 - 1) point-segment pairs).
+
+The continuous Frechet distance (csrc/tvq_traj_frechet.hip) is a leg of its own on the same
+pairs: `tvq_traj_frechet` on the packed batch with one workspace for all pairs, and its stages
+through `tvq_traj_frechet_stages` (critical values; critical values + sort and unique, whose
+difference is the sort's share; the search on what those left), device events, the same
+median.  Written under the key "frechet" with the probe count from the value count.
+
+Writes one JSON (default profiles/traj_dist_time.json) and prints it.
 
 usage: python tools/traj_dist_time.py [--runs 21] [--pairs 1024] [--n0 200] [--n1 300] [--out F]"""
 import argparse
@@ -115,6 +122,41 @@ res["rates"] = {"table_cells_per_s_per_geometry": cells / (res["ms"]["table"]["m
                 "segment_point_segment_pairs_per_s": segs / (res["ms"]["segment"]["median"] * 1e-3)}
 res["ms_per_pair_kernels"] = (res["ms"]["table"]["median"] + res["ms"]["segment"]["median"]) / P
 res["column_means"] = dict(zip(td.COLUMNS, full.mean(0).tolist()))
+
+# ---- the continuous Frechet distance ------------------------------------------------------
+need = td._frechet_bytes(h0, h1, 0, P)
+ws = torch.empty(need, dtype=torch.uint8, device=dev)
+fout = torch.zeros(P, dtype=torch.float64, device=dev)
+
+
+def frechet_stages(mask):
+    call("tvq_traj_frechet_stages", ptr(pts0), ptr(off0), ptr(pts1), ptr(off1), h0.ctypes.data,
+         h1.ctypes.data, P, ptr(fout), ptr(ws), need, mask, stream_ptr())
+
+
+def frechet_whole():
+    call("tvq_traj_frechet", ptr(pts0), ptr(off0), ptr(pts1), ptr(off1), h0.ctypes.data,
+         h1.ctypes.data, P, ptr(fout), ptr(ws), need, stream_ptr())
+
+
+frechet_whole()
+torch.cuda.synchronize()
+assert torch.equal(fout, td.frechet_device(gen, sim, device=dev, workspace_bytes=need))
+fr = {"workspace_bytes": need, "values_per_pair": 2 * (args.n0 - 1) * (args.n1 - 1) + 1, "ms": {}}
+fr["ms"]["whole"] = median_ms(frechet_whole, True)
+fr["ms"]["stage1_critical_values"] = median_ms(lambda: frechet_stages(1), True)
+fr["ms"]["stage1_and_2"] = median_ms(lambda: frechet_stages(3), True)
+fr["ms"]["stage3_search"] = median_ms(lambda: frechet_stages(4), True)
+fr["ms"]["end_to_end_from_host_float64"] = median_ms(
+    lambda: td.frechet_device(gen, sim, device=dev, workspace_bytes=need), False)
+fr["ms_stage2_sort_unique"] = (fr["ms"]["stage1_and_2"]["median"]
+                               - fr["ms"]["stage1_critical_values"]["median"])
+fr["ms_per_pair"] = fr["ms"]["whole"]["median"] / P
+fr["mean"] = float(fout.mean())
+res["frechet"] = fr
+for k, v in fr["ms"].items():
+    print(f"frechet {k:24s} median {v['median']:9.3f} ms  (min {v['min']:.3f}, max {v['max']:.3f})",
+          flush=True)
 for k, v in res["ms"].items():
     print(f"{k:32s} median {v['median']:9.3f} ms  (min {v['min']:.3f}, max {v['max']:.3f})", flush=True)
 os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
