@@ -796,6 +796,43 @@ int tvq_rocket_apply(const double* X, int64_t n, int64_t L, int64_t ldx, const d
 int tvq_fid_moments(const double* z, int64_t N, int64_t D, double* mu, double* cov,
                     tvq_stream_t stream);
 
+/* ---- FID end to end on the device (evaluation/eval_utils.py:56-81 calculate_fid;
+ * csrc/tvq_fid_sqrt.hip).  With A_i = (z_i - mu_i) / sqrt(N_i - 1), sigma_i = A_i^T A_i and
+ * tr sqrtm(sigma1 sigma2) = sum_k s_k(A1 A2^T): the trace of the matrix square root is a sum
+ * of singular values, computed here by one-sided Jacobi in float64 with no float atomics
+ * (two runs give the same bits).
+ * tvq_jacobi_sv: a holds n vectors of m_all doubles each, contiguous (vector j at
+ *   a + j m_all), orthogonalised in place by Hestenes rotations.  The first m_dot entries
+ *   enter the inner products and the rotation decisions, all m_all entries are rotated
+ *   (m_dot < m_all carries an accumulated rotation along: [S ; I] gives eigenvalues on top
+ *   and eigenvectors below).  Round-robin pairing, one launch per round (n - 1 rounds a sweep,
+ *   n when n is odd), one workgroup per pair; a pair is skipped when either vector is zero or
+ *   |a_p . a_q| <= 2^-52 sqrt(m_dot) |a_p| |a_q|.  All max_sweeps sweeps are enqueued; a
+ *   sweep whose predecessor made no rotation returns at once.  sigma (n) = the vectors'
+ *   2-norms over m_dot entries, unsorted; info = {sweeps that ran (the last one only
+ *   checks), converged 0/1}.  When the last sweep still rotated, sigma is all NaN and
+ *   converged is 0.  1 <= n <= 16384, 1 <= m_dot <= m_all <= 16384, 1 <= max_sweeps <= 64.
+ *   The workspace holds the sweep counters: tvq_jacobi_sv_workspace(n) bytes.
+ * tvq_fid_device: z1 (N1 x D), z2 (N2 x D) float64 row-major.  out = {fid, |mu1 - mu2|^2,
+ *   tr sigma1, tr sigma2, T} with fid = out[1] + out[2] + out[3] - 2 T, every sum in a fixed
+ *   order.  form 0 picks by shape, 1 forces "few", 2 forces "many":
+ *     few  (min(N1, N2) <= D): W = A1 A2^T with the min(N1, N2) vectors as rows, T = sum of the
+ *          row norms after Jacobi;
+ *     many (min(N1, N2) > D):  Jacobi on [sigma_i ; I] for i = 1, 2 gives F_i with rows
+ *          sqrt(lambda_j) v_j^T (F_i^T F_i = sigma_i), then T = sum s_k(F1 F2^T).
+ *   info = {form used (1 few, 2 many), sweeps of the sigma1, sigma2 and W runs (0, 0 and W's
+ *   for few), converged 0/1}; a run that did not converge makes fid and T NaN.
+ *   2 <= N1, N2 <= 16384, 1 <= D <= 2048, 1 <= max_sweeps <= 64; "few" needs
+ *   min(N1, N2) <= 2048.  tvq_fid_device_workspace returns the bytes for a (N1, N2, D, form)
+ *   (-1 with the error set for refused arguments); the workspace is 16-byte aligned. */
+int64_t tvq_jacobi_sv_workspace(int64_t n);
+int tvq_jacobi_sv(double* a, int64_t n, int64_t m_all, int64_t m_dot, int64_t max_sweeps,
+                  double* sigma, int32_t* info, void* workspace, tvq_stream_t stream);
+int64_t tvq_fid_device_workspace(int64_t N1, int64_t N2, int64_t D, int64_t form);
+int tvq_fid_device(const double* z1, int64_t N1, const double* z2, int64_t N2, int64_t D,
+                   int64_t form, int64_t max_sweeps, double* out, int32_t* info, void* workspace,
+                   tvq_stream_t stream);
+
 /* ---- TSGBench statistics (evaluation/stat_metrics.py:5-60 MDD / ACD / SD / KD;
  * csrc/tvq_stat.hip).  All float64; per-block partials go to `workspace` (the matching
  * *_workspace() count of doubles) and are added in a fixed order, so results are bitwise

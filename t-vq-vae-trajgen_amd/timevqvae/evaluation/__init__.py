@@ -1,14 +1,16 @@
 """Evaluation on the HIP path: ROCKET features (reference evaluation/rocket_functions.py),
-FID / IS (reference evaluation/eval_utils.py; the FID moments on the device), the TSGBench
+FID / IS (reference evaluation/eval_utils.py; the FID moments on the device, and with
+sqrtm="device" / `fid_device` the whole scalar: Jacobi singular values in float64), the TSGBench
 statistics MDD / ACD / SD / KD (reference evaluation/stat_metrics.py; KDE, autocorrelation
 and central moments on the device) and the `Metrics` class (reference evaluation/metrics.py)
 for the ROCKET extractor, and the flyability evaluation's trajectory distances (reference
 evaluation/flyability_eval.py calculate_trajectory_distances and flyability_utils/
-trajectory_distances; every table on the device).  The supervised FCN feature extractor, and
-with it the Inception Score of a trained classifier, is out of scope, as are the flyability
-evaluation's simulation, filtering and plotting and the continuous Frechet distance
+trajectory_distances; all 14, the continuous Frechet distance included, on the device).  The
+supervised FCN feature extractor, and with it the Inception Score of a trained classifier, is
+out of scope, as are the flyability evaluation's simulation, filtering and plotting
 (DESIGN.md)."""
-from .eval_utils import calculate_fid, calculate_inception_score, feature_moments
+from .eval_utils import (calculate_fid, calculate_inception_score, feature_moments,
+                         fid_device)
 from .flyability_eval import calculate_trajectory_distances
 from .flyability_utils import trajectory_distances_device
 from .metrics import Metrics
@@ -21,6 +23,6 @@ from .stat_metrics import (StatMetrics, auto_correlation_difference, kurtosis_di
 __all__ = ["DeviceKernels", "Metrics", "StatMetrics", "apply_kernel", "apply_kernels",
            "apply_kernels_device", "auto_correlation_difference", "calculate_fid",
            "calculate_inception_score", "calculate_trajectory_distances", "feature_moments",
-           "generate_kernels",
+           "fid_device", "generate_kernels",
            "kurtosis_difference", "marginal_distribution_difference", "skewness_difference",
            "stat_metrics_device", "trajectory_distances_device"]

@@ -92,9 +92,9 @@ class Metrics(nn.Module):
     def z_gen_fn(self, x_gen):
         return self.compute_z(x_gen)
 
-    def fid_score(self, z1: np.ndarray, z2: np.ndarray):
+    def fid_score(self, z1: np.ndarray, z2: np.ndarray, sqrtm: str = "host"):
         z1, z2 = remove_outliers(z1), remove_outliers(z2)
-        return calculate_fid(z1, z2, self.device)
+        return calculate_fid(z1, z2, self.device, sqrtm=sqrtm)
 
     def inception_score(self, x_gen):
         raise NotImplementedError("Metrics.inception_score: " + FCN_OUT_OF_SCOPE)

@@ -138,9 +138,9 @@ class TrainedModelSampler(nn.Module):
         """Features of generated samples (sampler.py:306-327)."""
         return batched(self._extract_feature_representations, X_gen, self.batch_size)
 
-    def fid_score(self, z1: np.ndarray, z2: np.ndarray):
+    def fid_score(self, z1: np.ndarray, z2: np.ndarray, sqrtm: str = "host"):
         z1, z2 = remove_outliers(z1), remove_outliers(z2)
-        return calculate_fid(z1, z2, self.device)
+        return calculate_fid(z1, z2, self.device, sqrtm=sqrtm)
 
     def inception_score(self, X_gen):
         raise NotImplementedError("TrainedModelSampler.inception_score: " + FCN_OUT_OF_SCOPE)

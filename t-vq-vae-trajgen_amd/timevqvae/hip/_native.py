@@ -255,6 +255,10 @@ F64 = ctypes.c_double
 sig("tvq_minmax_fit_workspace", I64, restype=I64)
 sig("tvq_minmax_fit", P, I64, I64, F64, F64, P, P, P, P, P, P)
 sig("tvq_fid_moments", P, I64, I64, P, P, P)
+sig("tvq_jacobi_sv_workspace", I64, restype=I64)
+sig("tvq_jacobi_sv", P, I64, I64, I64, I64, P, P, P, P)
+sig("tvq_fid_device_workspace", I64, I64, I64, I64, restype=I64)
+sig("tvq_fid_device", P, I64, P, I64, I64, I64, I64, P, P, P, P)
 # --- TSGBench statistics (MDD / ACD / SD / KD) --------------------------------
 sig("tvq_stat_moments_workspace", I64, restype=I64)
 sig("tvq_stat_moments", P, I64, P, P, P)

@@ -68,8 +68,10 @@ class Stage3(nn.Module):
     # ------------------------------------------------------------------ tau search
     @torch.no_grad()
     def search_optimal_tau(self, X_train: np.ndarray, device, n_samples: int = 1024,
-                           batch_size: int = 32, feature_fn=None):
-        """stage3.py:88-181.  feature_fn(X (n, c, l) float64) -> Z (n, d) overrides the
+                           batch_size: int = 32, feature_fn=None, fid_sqrtm: str = "host"):
+        """stage3.py:88-181.  fid_sqrtm is calculate_fid's `sqrtm` ("host": the reference's
+        scipy sqrtm; "device": evaluation.fid_device, the whole FID on the device).
+        feature_fn(X (n, c, l) float64) -> Z (n, d) overrides the
         extractor.  Without it the extractor follows feature_extractor_type as the reference's
         Metrics.extract_feature_representations does (metrics.py:107-127): 'rocket' uses the
         kernels drawn at construction; 'supervised_fcn' needs the pretrained FCN, which is
@@ -99,7 +101,8 @@ class Stage3(nn.Module):
                 xprime.append((maskgit.decode_token_ind_to_timeseries(sl, "lf")
                                + maskgit.decode_token_ind_to_timeseries(sh, "hf")).cpu())
             Zp = feature_fn(torch.cat(xprime).numpy().astype(float))
-            fids.append(float(calculate_fid(remove_outliers(Zhat), remove_outliers(Zp))))
+            fids.append(float(calculate_fid(remove_outliers(Zhat), remove_outliers(Zp),
+                                            sqrtm=fid_sqrtm)))
         self.tau_fids = dict(zip(self.tau_search_rng, fids))
         optimal_tau = self.tau_search_rng[int(np.argmin(fids))]
         self.fidelity_enhancer.tau = torch.tensor(optimal_tau).float().to(self.fidelity_enhancer.tau.device)
