@@ -19,7 +19,7 @@
 //
 // Every kernel writes per-block partials and a second launch adds them in a fixed order: no
 // float atomics, results are bitwise identical from run to run.
-#include "tvq_common.h"
+#include "tvq_eval.h"
 
 namespace tvq {
 namespace {
@@ -27,28 +27,6 @@ namespace {
 constexpr int ST_T = 256;          // threads per block, all kernels
 constexpr int ST_MAX_BLOCKS = 1024;
 constexpr int ST_PER_BLOCK = ST_T * 16;  // elements a block takes before the grid stops growing
-
-// Fixed-tree block sum over ST_T threads; the total in every thread.  red: ST_T doubles.
-__device__ __forceinline__ double block_sum_d(double v, double* red) {
-  __syncthreads();
-  red[threadIdx.x] = v;
-  __syncthreads();
-  for (int o = ST_T / 2; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-    __syncthreads();
-  }
-  return red[0];
-}
-__device__ __forceinline__ double block_min_d(double v, double* red) {
-  __syncthreads();
-  red[threadIdx.x] = v;
-  __syncthreads();
-  for (int o = ST_T / 2; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) red[threadIdx.x] = fmin(red[threadIdx.x], red[threadIdx.x + o]);
-    __syncthreads();
-  }
-  return red[0];
-}
 
 int64_t stat_blocks(int64_t n) {
   const int64_t b = (n + ST_PER_BLOCK - 1) / ST_PER_BLOCK;
@@ -69,9 +47,9 @@ __global__ __launch_bounds__(ST_T) void stat_sum_kernel(const double* __restrict
     lo = fmin(lo, v);
     nhi = fmin(nhi, -v);
   }
-  s = block_sum_d(s, red);
-  lo = block_min_d(lo, red);
-  nhi = block_min_d(nhi, red);
+  s = block_tree_sum_d<ST_T>(s, red);
+  lo = block_tree_min_d<ST_T>(lo, red);
+  nhi = block_tree_min_d<ST_T>(nhi, red);
   if (threadIdx.x == 0) {
     ws[blockIdx.x] = s;
     ws[nb + blockIdx.x] = lo;
@@ -91,9 +69,9 @@ __global__ __launch_bounds__(ST_T) void stat_sum_finish_kernel(const double* __r
     lo = fmin(lo, ws[nb + b]);
     nhi = fmin(nhi, ws[2 * nb + b]);
   }
-  s = block_sum_d(s, red);
-  lo = block_min_d(lo, red);
-  nhi = block_min_d(nhi, red);
+  s = block_tree_sum_d<ST_T>(s, red);
+  lo = block_tree_min_d<ST_T>(lo, red);
+  nhi = block_tree_min_d<ST_T>(nhi, red);
   if (threadIdx.x == 0) {
     out6[0] = lo;
     out6[1] = -nhi;
@@ -118,9 +96,9 @@ __global__ __launch_bounds__(ST_T) void stat_central_kernel(const double* __rest
     s3 += d2 * d;
     s4 += d2 * d2;
   }
-  s2 = block_sum_d(s2, red);
-  s3 = block_sum_d(s3, red);
-  s4 = block_sum_d(s4, red);
+  s2 = block_tree_sum_d<ST_T>(s2, red);
+  s3 = block_tree_sum_d<ST_T>(s3, red);
+  s4 = block_tree_sum_d<ST_T>(s4, red);
   if (threadIdx.x == 0) {
     ws[blockIdx.x] = s2;
     ws[nb + blockIdx.x] = s3;
@@ -139,9 +117,9 @@ __global__ __launch_bounds__(ST_T) void stat_central_finish_kernel(const double*
     s3 += ws[nb + b];
     s4 += ws[2 * nb + b];
   }
-  s2 = block_sum_d(s2, red);
-  s3 = block_sum_d(s3, red);
-  s4 = block_sum_d(s4, red);
+  s2 = block_tree_sum_d<ST_T>(s2, red);
+  s3 = block_tree_sum_d<ST_T>(s3, red);
+  s4 = block_tree_sum_d<ST_T>(s4, red);
   if (threadIdx.x == 0) {
     out6[3] = s2 / (double)n;
     out6[4] = s3 / (double)n;
@@ -151,12 +129,6 @@ __global__ __launch_bounds__(ST_T) void stat_central_finish_kernel(const double*
 
 // ---- Gaussian KDE ----------------------------------------------------------------------
 constexpr int KDE_GT = 10;  // grid points per thread (registers); blockIdx.y tiles the grid
-
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 
 // ws[blockIdx.x * G + g] = sum over this block's samples of exp(-(grid[g]/s - x[i]/s)^2 / 2)
 __global__ __launch_bounds__(ST_T) void kde_partial_kernel(const double* __restrict__ x, int64_t n,

@@ -26,7 +26,7 @@
 // No atomics: a pair's row is a function of that pair alone and is bitwise the same in any
 // batch.  Every comparison keeps the reference's form (a NaN along-track distance takes the
 // cross-track branch); this file must not be built with fast-math.
-#include "tvq_common.h"
+#include "tvq_eval.h"
 
 namespace tvq {
 namespace {
@@ -42,12 +42,6 @@ constexpr double TJ_R = 6378137.0;
 constexpr double TJ_RAD = 3.14159265358979323846 / 180.0;
 constexpr int TJ_COLS = 13;
 
-__device__ __forceinline__ double tj_eucl(double ax, double ay, double bx, double by) {
-#pragma clang fp contract(off)
-  const double dx = ax - bx, dy = ay - by;
-  return sqrt(dx * dx + dy * dy);
-}
-
 // great_circle_distance(lon1, lat1, lon2, lat2) with c1 = cos(rad lat1), c2 = cos(rad lat2)
 __device__ __forceinline__ double tj_hav(double lon1, double lat1, double c1, double lon2,
                                          double lat2, double c2) {
@@ -58,12 +52,6 @@ __device__ __forceinline__ double tj_hav(double lon1, double lat1, double c1, do
   const double a = sa * sa + c1 * c2 * so * so;
   const double c = 2.0 * atan2(sqrt(a), sqrt(1.0 - a));
   return TJ_R * c;
-}
-
-__device__ __forceinline__ double tj_wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
 }
 
 __device__ __forceinline__ double tj_min3(double a, double b, double c) {
@@ -102,16 +90,16 @@ __device__ void tj_table_sweep(const double* __restrict__ t0, int n0,
       cos1[j] = c;
       gp = tj_hav(g0, g1, cg, x, y, c);
     } else {
-      gp = tj_eucl(g0, g1, x, y);
+      gp = dist2d(g0, g1, x, y);
     }
     gap1[j] = gp;
     s1 += gp;
   }
   for (int i = lane; i < n0; i += TJ_W) {
     const double x = t0[2 * i], y = t0[2 * i + 1];
-    s0 += SPH ? tj_hav(g0, g1, cg, x, y, cos(TJ_RAD * y)) : tj_eucl(g0, g1, x, y);
+    s0 += SPH ? tj_hav(g0, g1, cg, x, y, cos(TJ_RAD * y)) : dist2d(g0, g1, x, y);
   }
-  const double total1 = tj_wave_sum(s1), total0 = tj_wave_sum(s0);
+  const double total1 = wave_sum_d(s1), total0 = wave_sum_d(s0);
   __syncthreads();
 
   // border values C[i >= 1][0] and C[0][j >= 1] of the real-valued recurrences
@@ -128,7 +116,7 @@ __device__ void tj_table_sweep(const double* __restrict__ t0, int n0,
     const int ic = (rowok ? i : n0) - 1;
     const double x0 = t0[2 * ic], y0 = t0[2 * ic + 1];
     const double c0 = SPH ? cos(TJ_RAD * y0) : 0.0;
-    const double gp0 = SPH ? tj_hav(x0, y0, c0, g0, g1, cg) : tj_eucl(g0, g1, x0, y0);
+    const double gp0 = SPH ? tj_hav(x0, y0, c0, g0, g1, cg) : dist2d(g0, g1, x0, y0);
     const int rows = n0 - b * TJ_W < TJ_W ? n0 - b * TJ_W : TJ_W;
     const bool feeds = b + 1 < nb && lane == TJ_W - 1;  // the band below reads this row
 
@@ -182,7 +170,7 @@ __device__ void tj_table_sweep(const double* __restrict__ t0, int n0,
           lf_c[1] = cur_c[1];
         }
         const double x1 = t1[2 * (j - 1)], y1 = t1[2 * (j - 1) + 1];
-        const double cost = SPH ? tj_hav(x0, y0, c0, x1, y1, cos1[j - 1]) : tj_eucl(x0, y0, x1, y1);
+        const double cost = SPH ? tj_hav(x0, y0, c0, x1, y1, cos1[j - 1]) : dist2d(x0, y0, x1, y1);
         cur_d[0] = cost + tj_min3(lf_d[0], dg_d[0], nu_d[0]);
         cur_d[1] = tj_min3(nu_d[1] + gp0, lf_d[1] + gap1[j - 1], dg_d[1] + cost);
         if constexpr (!SPH)
@@ -232,35 +220,6 @@ __global__ __launch_bounds__(TJ_W) void traj_table_kernel(
 }
 
 // ---- the segment family ------------------------------------------------------------------
-template <bool MAX>
-__device__ __forceinline__ double tj_block_reduce(double v, double* red) {
-  __syncthreads();
-  red[threadIdx.x] = v;
-  __syncthreads();
-  for (int o = TJ_ST / 2; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) {
-      const double a = red[threadIdx.x], b = red[threadIdx.x + o];
-      red[threadIdx.x] = MAX ? fmax(a, b) : a + b;
-    }
-    __syncthreads();
-  }
-  return red[0];
-}
-
-// basic_euclidean.point_to_seg
-__device__ __forceinline__ double tj_point_to_seg(double px, double py, double p1x, double p1y,
-                                                  double p2x, double p2y, double dps1,
-                                                  double dps2, double segl) {
-#pragma clang fp contract(off)
-  if (p1x == p2x && p1y == p2y) return dps1;
-  const double xd = p2x - p1x, yd = p2y - p1y;
-  const double u1 = ((px - p1x) * xd) + ((py - p1y) * yd);
-  const double u = u1 / (segl * segl);
-  if ((u < 0.00001) || (u > 1.0)) return fmin(dps1, dps2);
-  const double ix = p1x + u * xd, iy = p1y + u * yd;
-  return tj_eucl(px, py, ix, iy);
-}
-
 // basic_spherical.point_to_path; th12 the segment's initial bearing, (c1, s1) = cos / sin of
 // rad lat1, (c3, s3) of rad lat3
 __device__ __forceinline__ double tj_point_to_path(double lon1, double c1, double s1, double th12,
@@ -320,7 +279,7 @@ __global__ __launch_bounds__(TJ_ST) void traj_segment_kernel(
         }
         __syncthreads();
         for (int m = tid; m < nseg; m += TJ_ST) {
-          sds[m] = tj_eucl(sx[m], sy[m], sx[m + 1], sy[m + 1]);
+          sds[m] = dist2d(sx[m], sy[m], sx[m + 1], sy[m + 1]);
           sd12[m] = tj_hav(sx[m], sy[m], sc[m], sx[m + 1], sy[m + 1], sc[m + 1]);
           // initial_bearing(segment start -> segment end)
           const double dlon = TJ_RAD * (sx[m + 1] - sx[m]);
@@ -331,15 +290,15 @@ __global__ __launch_bounds__(TJ_ST) void traj_segment_kernel(
         __syncthreads();
         if (valid) {
           // the pairwise distances are those of (t0 point, t1 point) in both directions
-          double dps1 = dir == 0 ? tj_eucl(px, py, sx[0], sy[0]) : tj_eucl(sx[0], sy[0], px, py);
+          double dps1 = dir == 0 ? dist2d(px, py, sx[0], sy[0]) : dist2d(sx[0], sy[0], px, py);
           double d13 = dir == 0 ? tj_hav(px, py, cp, sx[0], sy[0], sc[0])
                                 : tj_hav(sx[0], sy[0], sc[0], px, py, cp);
           for (int m = 0; m < nseg; ++m) {
             const double qx = sx[m + 1], qy = sy[m + 1], qc = sc[m + 1];
-            const double dps2 = dir == 0 ? tj_eucl(px, py, qx, qy) : tj_eucl(qx, qy, px, py);
+            const double dps2 = dir == 0 ? dist2d(px, py, qx, qy) : dist2d(qx, qy, px, py);
             const double d23 = dir == 0 ? tj_hav(px, py, cp, qx, qy, qc)
                                         : tj_hav(qx, qy, qc, px, py, cp);
-            me = fmin(me, tj_point_to_seg(px, py, sx[m], sy[m], qx, qy, dps1, dps2, sds[m]));
+            me = fmin(me, point_to_seg(px, py, sx[m], sy[m], qx, qy, dps1, dps2, sds[m]));
             ms = fmin(ms, tj_point_to_path(sx[m], sc[m], ss[m], sth[m], sd12[m], px, cp, sp, d13,
                                            d23));
             dps1 = dps2;
@@ -354,10 +313,10 @@ __global__ __launch_bounds__(TJ_ST) void traj_segment_kernel(
         top_s = fmax(top_s, ms);
       }
     }
-    mean_e[dir] = tj_block_reduce<false>(sum_e, red) / (double)nA;
-    mean_s[dir] = tj_block_reduce<false>(sum_s, red) / (double)nA;
-    max_e[dir] = tj_block_reduce<true>(top_e, red);
-    max_s[dir] = tj_block_reduce<true>(top_s, red);
+    mean_e[dir] = block_tree_sum_d<TJ_ST>(sum_e, red) / (double)nA;
+    mean_s[dir] = block_tree_sum_d<TJ_ST>(sum_s, red) / (double)nA;
+    max_e[dir] = block_tree_max_d<TJ_ST>(top_e, red);
+    max_s[dir] = block_tree_max_d<TJ_ST>(top_s, red);
   }
   if (tid == 0) {
     double* orow = out + p * TJ_COLS;
@@ -366,28 +325,6 @@ __global__ __launch_bounds__(TJ_ST) void traj_segment_kernel(
     orow[4] = fmax(max_e[0], max_e[1]);
     orow[5] = fmax(max_s[1], max_s[0]);
   }
-}
-
-// Lengths of every pair from the host copy of the offsets; false (error set) outside
-// [nmin, TJ_MAX_LEN].  *max1 = the longest t1.
-bool tj_check(const char* what, const int64_t* h0, const int64_t* h1, int64_t P, int64_t nmin,
-              int64_t* max1) {
-  *max1 = 0;
-  for (int64_t p = 0; p < P; ++p) {
-    const int64_t n0 = h0[p + 1] - h0[p], n1 = h1[p + 1] - h1[p];
-    if (h0[p] < 0 || h1[p] < 0 || n0 < nmin || n1 < nmin) {
-      set_error("%s: pair %lld has %lld and %lld points, at least %lld each are needed", what,
-                (long long)p, (long long)n0, (long long)n1, (long long)nmin);
-      return false;
-    }
-    if (n0 > TJ_MAX_LEN || n1 > TJ_MAX_LEN) {
-      set_error("%s: pair %lld has %lld and %lld points, the limit is %lld", what, (long long)p,
-                (long long)n0, (long long)n1, (long long)TJ_MAX_LEN);
-      return false;
-    }
-    if (n1 > *max1) *max1 = n1;
-  }
-  return true;
 }
 
 }  // namespace
@@ -407,8 +344,10 @@ extern "C" int tvq_traj_table_distances(const double* pts0, const int64_t* off0,
   if (P == 0) return TVQ_OK;
   TVQ_CHECK_ARG(pts0 && off0 && pts1 && off1 && host_off0 && host_off1 && out,
                 "tvq_traj_table_distances: bad arguments");
-  int64_t max1 = 0;
-  if (!tj_check("tvq_traj_table_distances", host_off0, host_off1, P, 1, &max1)) return TVQ_ERR_ARG;
+  int64_t max1 = 0;  // the longest t1 sizes the LDS
+  if (!check_ragged_pairs("tvq_traj_table_distances", host_off0, host_off1, P, 1, TJ_MAX_LEN,
+                          [&](int64_t, int64_t n1) { max1 = n1 > max1 ? n1 : max1; }))
+    return TVQ_ERR_ARG;
   // above 64 KiB of dynamic LDS a kernel has to opt in (a gfx950 CU has 160 KiB)
   static bool attr = [] {
     (void)hipFuncSetAttribute((const void*)traj_table_kernel,
@@ -432,8 +371,8 @@ extern "C" int tvq_traj_segment_distances(const double* pts0, const int64_t* off
   if (P == 0) return TVQ_OK;
   TVQ_CHECK_ARG(pts0 && off0 && pts1 && off1 && host_off0 && host_off1 && out,
                 "tvq_traj_segment_distances: bad arguments");
-  int64_t max1 = 0;
-  if (!tj_check("tvq_traj_segment_distances", host_off0, host_off1, P, 2, &max1))
+  if (!check_ragged_pairs("tvq_traj_segment_distances", host_off0, host_off1, P, 2, TJ_MAX_LEN,
+                          [](int64_t, int64_t) {}))
     return TVQ_ERR_ARG;
   hipLaunchKernelGGL(traj_segment_kernel, dim3((unsigned)P), dim3(TJ_ST), 0, (hipStream_t)stream,
                      pts0, off0, pts1, off1, out);

@@ -32,11 +32,11 @@
 //                          The interval end points are evaluated only where the reference
 //                          reads them: the four corner cells, column 0 and row 0.
 //
-// The distances (mdist, P_dist, Q_dist of the reference) are never stored: fr_dist recomputes
-// them in stages 1 and 3 alike, and both stages call the one fr_point_to_seg, so a critical
+// The distances (mdist, P_dist, Q_dist of the reference) are never stored: dist2d recomputes
+// them in stages 1 and 3 alike, and both stages call the one point_to_seg, so a critical
 // value probed as eps sees `point_to_seg > eps` false in its own cell, exactly.  No atomics,
 // a pair's value depends on that pair alone.  This file must not be built with fast-math.
-#include "tvq_common.h"
+#include "tvq_eval.h"
 
 namespace tvq {
 namespace {
@@ -56,26 +56,6 @@ __host__ __device__ inline int64_t fr_cap(int64_t n0, int64_t n1) {
   return (v + FR_TILE - 1) / FR_TILE * FR_TILE;
 }
 
-__device__ __forceinline__ double fr_dist(double ax, double ay, double bx, double by) {
-#pragma clang fp contract(off)
-  const double dx = ax - bx, dy = ay - by;
-  return sqrt(dx * dx + dy * dy);
-}
-
-// basic_euclidean.point_to_seg
-__device__ __forceinline__ double fr_point_to_seg(double px, double py, double p1x, double p1y,
-                                                  double p2x, double p2y, double dps1,
-                                                  double dps2, double segl) {
-#pragma clang fp contract(off)
-  if (p1x == p2x && p1y == p2y) return dps1;
-  const double xd = p2x - p1x, yd = p2y - p1y;
-  const double u1 = ((px - p1x) * xd) + ((py - p1y) * yd);
-  const double u = u1 / (segl * segl);
-  if ((u < 0.00001) || (u > 1.0)) return dps2 < dps1 ? dps2 : dps1;
-  const double ix = p1x + u * xd, iy = p1y + u * yd;
-  return fr_dist(px, py, ix, iy);
-}
-
 // frechet.free_line with basic_euclidean.circle_line_intersection inlined
 __device__ __forceinline__ FrIv fr_free_line(double px, double py, double s1x, double s1y,
                                              double s2x, double s2y, double dps1, double dps2,
@@ -86,7 +66,7 @@ __device__ __forceinline__ FrIv fr_free_line(double px, double py, double s1x, d
     if (dps1 > eps) return none;
     return FrIv{0.0, 1.0};
   }
-  if (fr_point_to_seg(px, py, s1x, s1y, s2x, s2y, dps1, dps2, ds) > eps) return none;
+  if (point_to_seg(px, py, s1x, s1y, s2x, s2y, dps1, dps2, ds) > eps) return none;
   const double segl2 = ds * ds;
   double x1, y1, x2, y2;
   if (s2x == s1x) {
@@ -131,7 +111,7 @@ __device__ __forceinline__ bool fr_some(FrIv v) { return !(v.lo == -1.0 && v.hi 
 __device__ __forceinline__ bool fr_full(FrIv v) { return v.lo == 0.0 && v.hi == 1.0; }
 
 // One pair: P (p points) and Q (q points), row-major (n, 2).  The four functions below are the
-// only places a distance is formed, always as fr_dist(point of P or segment start, ...).
+// only places a distance is formed, always as dist2d(point of P or segment start, ...).
 struct FrPair {
   const double* __restrict__ P;
   const double* __restrict__ Q;
@@ -142,29 +122,29 @@ struct FrPair {
 __device__ __forceinline__ double fr_L(const FrPair& t, int i, int j) {
   const double ax = t.P[2 * i], ay = t.P[2 * i + 1], bx = t.P[2 * i + 2], by = t.P[2 * i + 3];
   const double qx = t.Q[2 * j], qy = t.Q[2 * j + 1];
-  return fr_point_to_seg(qx, qy, ax, ay, bx, by, fr_dist(ax, ay, qx, qy), fr_dist(bx, by, qx, qy),
-                         fr_dist(ax, ay, bx, by));
+  return point_to_seg(qx, qy, ax, ay, bx, by, dist2d(ax, ay, qx, qy), dist2d(bx, by, qx, qy),
+                      dist2d(ax, ay, bx, by));
 }
 // Bij: point_to_seg(P[i], Q[j], Q[j + 1], mdist[i, j], mdist[i, j + 1], Q_dist[j])
 __device__ __forceinline__ double fr_B(const FrPair& t, int i, int j) {
   const double ax = t.Q[2 * j], ay = t.Q[2 * j + 1], bx = t.Q[2 * j + 2], by = t.Q[2 * j + 3];
   const double px = t.P[2 * i], py = t.P[2 * i + 1];
-  return fr_point_to_seg(px, py, ax, ay, bx, by, fr_dist(px, py, ax, ay), fr_dist(px, py, bx, by),
-                         fr_dist(ax, ay, bx, by));
+  return point_to_seg(px, py, ax, ay, bx, by, dist2d(px, py, ax, ay), dist2d(px, py, bx, by),
+                      dist2d(ax, ay, bx, by));
 }
 // LF[(i, j)]: the free part of segment [P[i], P[i + 1]] seen from Q[j]; i <= p - 2, j <= q - 1
 __device__ __forceinline__ FrIv fr_LF(const FrPair& t, int i, int j, double eps) {
   const double ax = t.P[2 * i], ay = t.P[2 * i + 1], bx = t.P[2 * i + 2], by = t.P[2 * i + 3];
   const double qx = t.Q[2 * j], qy = t.Q[2 * j + 1];
-  return fr_free_line(qx, qy, ax, ay, bx, by, fr_dist(ax, ay, qx, qy), fr_dist(bx, by, qx, qy),
-                      fr_dist(ax, ay, bx, by), eps);
+  return fr_free_line(qx, qy, ax, ay, bx, by, dist2d(ax, ay, qx, qy), dist2d(bx, by, qx, qy),
+                      dist2d(ax, ay, bx, by), eps);
 }
 // BF[(i, j)]: the free part of segment [Q[j], Q[j + 1]] seen from P[i]; i <= p - 1, j <= q - 2
 __device__ __forceinline__ FrIv fr_BF(const FrPair& t, int i, int j, double eps) {
   const double ax = t.Q[2 * j], ay = t.Q[2 * j + 1], bx = t.Q[2 * j + 2], by = t.Q[2 * j + 3];
   const double px = t.P[2 * i], py = t.P[2 * i + 1];
-  return fr_free_line(px, py, ax, ay, bx, by, fr_dist(px, py, ax, ay), fr_dist(px, py, bx, by),
-                      fr_dist(ax, ay, bx, by), eps);
+  return fr_free_line(px, py, ax, ay, bx, by, dist2d(px, py, ax, ay), dist2d(px, py, bx, by),
+                      dist2d(ax, ay, bx, by), eps);
 }
 
 __device__ __forceinline__ bool fr_load_pair(const double* pts0, const int64_t* off0,
@@ -229,9 +209,9 @@ __global__ __launch_bounds__(FR_T) void fr_critical_kernel(
   const int64_t V = 2 * cells + 1;
   if (cap != fr_cap(t.p, t.q)) return;  // the layout is this pair's own
   u64* dst = buf + voff[pr];
-  const double origin = fr_dist(t.P[0], t.P[1], t.Q[0], t.Q[1]);
-  const double end = fr_dist(t.P[2 * (t.p - 1)], t.P[2 * (t.p - 1) + 1], t.Q[2 * (t.q - 1)],
-                             t.Q[2 * (t.q - 1) + 1]);
+  const double origin = dist2d(t.P[0], t.P[1], t.Q[0], t.Q[1]);
+  const double end = dist2d(t.P[2 * (t.p - 1)], t.P[2 * (t.p - 1) + 1], t.Q[2 * (t.q - 1)],
+                            t.Q[2 * (t.q - 1) + 1]);
   const double end_point = end > origin ? end : origin;
   int64_t n = cells > cap - V ? cells : cap - V;
   if (n < 1) n = 1;
@@ -468,29 +448,17 @@ __global__ __launch_bounds__(FR_T) void fr_search_kernel(
 
 constexpr int64_t FR_MAX_PAIRS = 65536;
 
-// Lengths from the host offsets; the total of fr_cap and the largest one.  False (error set)
-// for a pair outside [1, max_len].
-bool fr_check(const char* what, const int64_t* h0, const int64_t* h1, int64_t P, int64_t max_len,
+// From the host offsets: the total of fr_cap, the largest one and the most cells of a pair.
+// False (error set) for a pair outside [1, max_len].
+bool fr_sizes(const char* what, const int64_t* h0, const int64_t* h1, int64_t P, int64_t max_len,
               int64_t* total, int64_t* cap_max, int64_t* cells_max) {
   *total = *cap_max = *cells_max = 0;
-  for (int64_t p = 0; p < P; ++p) {
-    const int64_t n0 = h0[p + 1] - h0[p], n1 = h1[p + 1] - h1[p];
-    if (h0[p] < 0 || h1[p] < 0 || n0 < 1 || n1 < 1) {
-      set_error("%s: pair %lld has %lld and %lld points, at least 1 each is needed", what,
-                (long long)p, (long long)n0, (long long)n1);
-      return false;
-    }
-    if (n0 > max_len || n1 > max_len) {
-      set_error("%s: pair %lld has %lld and %lld points, the limit is %lld", what, (long long)p,
-                (long long)n0, (long long)n1, (long long)max_len);
-      return false;
-    }
+  return check_ragged_pairs(what, h0, h1, P, 1, max_len, [&](int64_t n0, int64_t n1) {
     const int64_t cap = fr_cap(n0, n1), cells = (n0 - 1) * (n1 - 1);
     *total += cap;
     if (cap > *cap_max) *cap_max = cap;
     if (cells > *cells_max) *cells_max = cells;
-  }
-  return true;
+  });
 }
 
 int64_t fr_head_bytes(int64_t P) { return ((2 * P + 1) * (int64_t)sizeof(int64_t) + 255) / 256 * 256; }
@@ -509,7 +477,7 @@ extern "C" int64_t tvq_traj_frechet_workspace(const int64_t* host_off0, const in
   }
   if (P == 0) return 0;
   int64_t total, cap_max, cells_max;
-  if (!fr_check("tvq_traj_frechet_workspace", host_off0, host_off1, P, tvq_traj_max_len(), &total,
+  if (!fr_sizes("tvq_traj_frechet_workspace", host_off0, host_off1, P, tvq_traj_max_len(), &total,
                 &cap_max, &cells_max))
     return -1;
   return fr_head_bytes(P) + 2 * total * (int64_t)sizeof(u64);
@@ -528,7 +496,7 @@ extern "C" int tvq_traj_frechet_stages(const double* pts0, const int64_t* off0,
                 "tvq_traj_frechet: bad arguments");
   const int64_t max_len = tvq_traj_max_len();
   int64_t total, cap_max, cells_max;
-  if (!fr_check("tvq_traj_frechet", host_off0, host_off1, P, max_len, &total, &cap_max, &cells_max))
+  if (!fr_sizes("tvq_traj_frechet", host_off0, host_off1, P, max_len, &total, &cap_max, &cells_max))
     return TVQ_ERR_ARG;
   const int64_t need = fr_head_bytes(P) + 2 * total * (int64_t)sizeof(u64);
   TVQ_CHECK_ARG(workspace_bytes >= need && ((uintptr_t)workspace & 7) == 0,

@@ -5,7 +5,7 @@ the O(N D^2) part, run on the device in float64 (tvq_fid_moments, csrc/tvq_fid.h
 D x D remainder -- sigma1 @ sigma2, its matrix square root (scipy.linalg.sqrtm, real part
 when complex) and the trace -- stays on the host in float64 as in the reference.  That is the
 default.  calculate_fid(..., sqrtm="device") / fid_device run the whole scalar on the device
-instead (tvq_fid_device, csrc/tvq_fid_sqrt.hip): tr sqrtm(sigma1 sigma2) is the sum of the
+instead (tvq_fid_device, csrc/tvq_fid.hip): tr sqrtm(sigma1 sigma2) is the sum of the
 singular values of A1 A2^T, A_i = (z_i - mu_i) / sqrt(N_i - 1), found by one-sided Jacobi in
 float64 (DESIGN.md).
 
@@ -17,12 +17,13 @@ import torch
 from scipy.linalg import sqrtm as host_sqrtm
 
 from ..hip._native import call, lib, ptr, stream_ptr, value
+from ._device import resolve_device
 
 
 def feature_moments(z, device=None):
     """(mu (D,), sigma (D, D)) of the rows of z (N, D): z.mean(0) and
     np.cov(z, rowvar=False), float64 on the device."""
-    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    dev = resolve_device(device)
     zt = torch.as_tensor(z)
     if zt.dim() != 2 or zt.shape[0] < 2:
         raise ValueError("feature_moments: z must be (N >= 2, D)")
@@ -47,7 +48,7 @@ def fid_device(z1, z2, device=None, form="auto", max_sweeps=40, return_parts=Fal
     converged), both on the device."""
     if form not in FID_FORMS:
         raise ValueError(f"fid_device: form must be one of {sorted(FID_FORMS)}, got {form!r}")
-    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    dev = resolve_device(device)
     zs = [torch.as_tensor(z) for z in (z1, z2)]
     if any(z.dim() != 2 or z.shape[0] < 2 for z in zs) or zs[0].shape[1] != zs[1].shape[1]:
         raise ValueError("fid_device: z1, z2 must be (N1 >= 2, D) and (N2 >= 2, D)")

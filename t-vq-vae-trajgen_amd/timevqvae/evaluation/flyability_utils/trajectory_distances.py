@@ -26,6 +26,7 @@ import numpy as np
 import torch
 
 from ...hip._native import call, ptr, stream_ptr, value
+from .._device import resolve_device
 
 COLUMNS = ("SSPD Euclidean", "SSPD Spherical", "DTW Euclidean", "DTW Spherical",
            "Hausdorff Euclidean", "Hausdorff Spherical", "LCSS Euclidean", "LCSS Spherical",
@@ -81,6 +82,20 @@ def _pack(t0s, t1s, dev):
     return (pts[:2 * n0], offs[:P1], pts[2 * n0:2 * (n0 + n1)], offs[P1:], h0, h1)
 
 
+def _prepare(gen, sim, need):
+    """The shared opening of the batch functions: (t0s, t1s), the checked tensors of two lists
+    of equal length.  need: the fewest points a trajectory may have, or a function that returns
+    it (and may refuse other arguments), called once the lengths are known to agree."""
+    gen, sim = list(gen), list(sim)
+    if len(gen) != len(sim):
+        raise ValueError(f"trajectory_distances: {len(gen)} generated and {len(sim)} simulated "
+                         f"trajectories")
+    if callable(need):
+        need = need()
+    return ([_as_tensor(a, "gen", k, need) for k, a in enumerate(gen)],
+            [_as_tensor(a, "sim", k, need) for k, a in enumerate(sim)])
+
+
 def trajectory_distances_device(gen, sim, g, eps=0.009, lcss_spherical_eps=None,
                                 edr_spherical_eps=None, device=None, families=FAMILIES):
     """(P, 13) float64 device tensor: row p holds the COLUMNS distances of (gen[p], sim[p]).
@@ -90,25 +105,19 @@ def trajectory_distances_device(gen, sim, g, eps=0.009, lcss_spherical_eps=None,
     spherical LCSS uses lcss_spherical_eps (default eps * 1e6) and spherical EDR
     edr_spherical_eps (default eps), as the reference's caller passes them.  families: which
     kernel families run; the columns of the other one are nan."""
-    gen, sim = list(gen), list(sim)
-    if len(gen) != len(sim):
-        raise ValueError(f"trajectory_distances: {len(gen)} generated and {len(sim)} simulated "
-                         f"trajectories")
     families = tuple(families)
-    if not families or any(f not in FAMILIES for f in families):
-        raise ValueError(f"trajectory_distances: families must be chosen from {FAMILIES}")
-    need = 2 if "segment" in families else 1
-    t0s = [_as_tensor(a, "gen", k, need) for k, a in enumerate(gen)]
-    t1s = [_as_tensor(a, "sim", k, need) for k, a in enumerate(sim)]
+
+    def need():
+        if not families or any(f not in FAMILIES for f in families):
+            raise ValueError(f"trajectory_distances: families must be chosen from {FAMILIES}")
+        return 2 if "segment" in families else 1
+
+    t0s, t1s = _prepare(gen, sim, need)
     g0, g1 = (float(v) for v in g)
     eps = float(eps)
     eps_ls = eps * 1e6 if lcss_spherical_eps is None else float(lcss_spherical_eps)
     eps_es = eps if edr_spherical_eps is None else float(edr_spherical_eps)
-    if device is not None:
-        dev = torch.device(device)
-    else:
-        cuda = [t.device for t in t0s + t1s if t.is_cuda]
-        dev = cuda[0] if cuda else torch.device("cuda", torch.cuda.current_device())
+    dev = resolve_device(device, t0s + t1s)
     P = len(t0s)
     if P == 0:
         return torch.empty((0, len(COLUMNS)), dtype=torch.float64, device=dev)
@@ -220,18 +229,9 @@ def frechet_device(gen, sim, device=None, workspace_bytes=1 << 30):
     device, take 32 (n0 - 1)(n1 - 1) bytes of workspace: the batch runs in chunks of
     consecutive pairs that fit `workspace_bytes`, and a single pair that does not is refused.
     A pair's value does not depend on the batch or the chunking (bitwise)."""
-    gen, sim = list(gen), list(sim)
-    if len(gen) != len(sim):
-        raise ValueError(f"trajectory_distances: {len(gen)} generated and {len(sim)} simulated "
-                         f"trajectories")
-    t0s = [_as_tensor(a, "gen", k, 1) for k, a in enumerate(gen)]
-    t1s = [_as_tensor(a, "sim", k, 1) for k, a in enumerate(sim)]
+    t0s, t1s = _prepare(gen, sim, 1)
     chunks = _frechet_chunks(_offsets(t0s), _offsets(t1s), int(workspace_bytes))
-    if device is not None:
-        dev = torch.device(device)
-    else:
-        cuda = [t.device for t in t0s + t1s if t.is_cuda]
-        dev = cuda[0] if cuda else torch.device("cuda", torch.cuda.current_device())
+    dev = resolve_device(device, t0s + t1s)
     P = len(t0s)
     if P == 0:
         return torch.empty((0,), dtype=torch.float64, device=dev)

@@ -13,6 +13,7 @@ import numpy as np
 import torch
 
 from ..hip._native import call, ptr, stream_ptr
+from ._device import resolve_device
 
 MAX_KERNEL_LENGTH = 16
 
@@ -88,8 +89,7 @@ def apply_kernels_device(X, dk):
 
 def apply_kernels(X, kernels, device=None):
     """rocket_functions.py:91-126: X (n, L) -> (n, 2 * num_kernels) float64 numpy."""
-    device = torch.device(device) if device is not None else torch.device(
-        "cuda", torch.cuda.current_device())
+    device = resolve_device(device)
     dk = kernels if isinstance(kernels, DeviceKernels) else DeviceKernels(kernels, device)
     Xt = torch.as_tensor(np.ascontiguousarray(X, dtype=np.float64)).to(dk.device)
     return apply_kernels_device(Xt, dk).cpu().numpy()

@@ -23,6 +23,7 @@ import numpy as np
 import torch
 
 from ..hip._native import call, ptr, stream_ptr, value
+from ._device import resolve_device
 
 GRID_POINTS = 100
 
@@ -39,12 +40,7 @@ def _upload(a, device=None):
     if t.dtype not in (torch.float32, torch.float64):
         raise ValueError(f"stat_metrics: expected float32 or float64, got {t.dtype}")
     eps = float(torch.finfo(t.dtype).eps)
-    if device is not None:
-        dev = torch.device(device)
-    elif t.is_cuda:
-        dev = t.device
-    else:
-        dev = torch.device("cuda", torch.cuda.current_device())
+    dev = resolve_device(device, (t,))
     # copy in the input's dtype, widen on the device: a float32 set crosses the bus once, as is
     return t.detach().to(dev).to(torch.float64).contiguous(), eps
 

@@ -1,4 +1,4 @@
-"""One-sided Jacobi singular values (tvq_jacobi_sv, csrc/tvq_fid_sqrt.hip): the kernel under
+"""One-sided Jacobi singular values (tvq_jacobi_sv, csrc/tvq_fid.hip): the kernel under
 evaluation.fid_device, exposed alone so it can be tested alone."""
 import torch
 
