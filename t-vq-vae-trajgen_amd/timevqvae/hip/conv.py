@@ -11,22 +11,23 @@ import os
 import torch
 
 from . import rng, streams
-from ._native import call, grad_sink, ptr, stream_ptr, value
+from ._native import call, grad_buffer, grad_sink, ptr, stream_ptr, value
 
 
 def _ws(n, dev):
     return torch.empty(max(int(n), 1), device=dev, dtype=torch.float32)
 
 
-def _bias_grad(g, dev, sink=None):
-    """Per-channel sum of g (B, C, ...) -> returned tensor, or accumulated into `sink`."""
+def _bias_grad(g, b_p):
+    """Per-channel sum of g (B, C, ...), the gradient of the bias b_p: returned, or accumulated
+    into b_p's flat-gradient view (then None; off the critical path: aux stream)."""
     B, C = g.shape[0], g.shape[1]
     HW = g.numel() // (B * C)
-    out = sink if sink is not None else torch.empty(C, device=dev, dtype=torch.float32)
-    ws = _ws(value("tvq_channel_sum_workspace", B, C, HW), dev)
-    call("tvq_channel_sum", ptr(g), B, C, HW, ptr(out), int(sink is not None), ptr(ws),
-         stream_ptr())
-    return None if sink is not None else out
+    out, direct = grad_buffer(b_p)
+    with (streams.offload(g) if direct else contextlib.nullcontext()):
+        ws = _ws(value("tvq_channel_sum_workspace", B, C, HW), g.device)
+        call("tvq_channel_sum", ptr(g), B, C, HW, ptr(out), int(direct), ptr(ws), stream_ptr())
+    return None if direct else out
 
 
 USE_WORKSPACE = True  # tests flip this to cover the no-workspace (in-place weight) path
@@ -154,8 +155,7 @@ class _Conv2d(torch.autograd.Function):
         Wo = value("tvq_conv_out_width", Wi, KW, SW, 0)
         y = torch.empty((B, Co, H, Wo), device=x.device, dtype=torch.float32)
         res = _as4d(residual).contiguous() if residual is not None else None
-        seed = rng.seed_tensor(x.device) if drop_p > 0 else None
-        off = rng.call_offset(site) if drop_p > 0 else 0
+        seed, off = rng.draw(x.device, site, drop_p > 0)
         ws = _conv_ws(OP_FWD, x.device, B, Ci, H, Wi, Co, KH, KW, SW)
         call("tvq_conv2d_fwd", ptr(x4), B, Ci, H, Wi, ptr(w4), ptr(b), Co, KH, KW, SW,
              int(replicate), ptr(y), ptr(res), float(drop_p), ptr(seed), off, ptr(ws),
@@ -257,19 +257,16 @@ class _ConvT2d(torch.autograd.Function):
                  ptr(ws), s)
         w_p, b_p = ctx.params
         if ctx.needs_input_grad[1]:
-            sw = grad_sink(w_p)
-            with (streams.offload(x, g) if sw is not None else contextlib.nullcontext()):
-                dwt = sw if sw is not None else torch.empty_like(w)
+            dwt, direct = grad_buffer(w_p)
+            with (streams.offload(x, g) if direct else contextlib.nullcontext()):
                 ws = _conv_ws(OP_T_WGRAD, x.device, B, Ci, H, Wi, Co, KH, KW, SW, required=True)
-                with _immediate(sw is None):
+                with _immediate(not direct):
                     call("tvq_convT2d_wgrad", ptr(x), B, Ci, H, Wi, ptr(g), Co, Wo, KH, KW, SW,
-                         ptr(dwt), int(sw is not None), ptr(ws), stream_ptr())
+                         ptr(dwt), int(direct), ptr(ws), stream_ptr())
                 _keep(ws)
-            dw = None if sw is not None else dwt
+            dw = None if direct else dwt
         if ctx.has_b and ctx.needs_input_grad[2]:
-            sb = grad_sink(b_p)
-            with (streams.offload(g) if sb is not None else contextlib.nullcontext()):
-                db = _bias_grad(g, x.device, sb)
+            db = _bias_grad(g, b_p)
         return dx, dw, db, None
 
 

@@ -61,8 +61,7 @@ class _GNSnake(torch.autograd.Function):
         y = torch.empty_like(x)
         mean = torch.empty(B * groups, device=x.device)
         rstd = torch.empty(B * groups, device=x.device)
-        seed = rng.seed_tensor(x.device) if drop_p > 0 else None
-        off = rng.call_offset(site) if drop_p > 0 else 0
+        seed, off = rng.draw(x.device, site, drop_p > 0)
         res = _c(residual) if residual is not None else None
         call("tvq_fe_gn_snake_train_fwd", ptr(x), B, C, L, int(groups), ptr(_c(gamma)),
              ptr(_c(beta)), ptr(_c(a).reshape(-1)), float(eps), float(drop_p), ptr(seed), off,

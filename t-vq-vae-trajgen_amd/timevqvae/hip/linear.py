@@ -1,8 +1,10 @@
 """Dense GEMM ops (nn.Linear over the last dim) on the HIP path."""
+import contextlib
+
 import torch
 
 from . import streams, wgrad
-from ._native import call, grad_sink, ptr, stream_ptr, value
+from ._native import call, grad_buffer, grad_sink, ptr, stream_ptr, value
 
 
 def gemm(A, sam, sak, B, sbk, sbn, M, N, K, out=None, ldc=None, alpha=1.0, bias=None, R=None,
@@ -22,15 +24,13 @@ def gemm(A, sam, sak, B, sbk, sbn, M, N, K, out=None, ldc=None, alpha=1.0, bias=
 def _bias_grad_rows(g2, sink=None):
     """Column sums of a row-major (M, N) gradient: returned, or accumulated into `sink`."""
     M, N = g2.shape
-    if sink is not None:  # into the flat gradient: off the critical path
-        with streams.offload(g2):
-            ws = torch.empty(value("tvq_channel_sum_workspace", M, N, 1), device=g2.device)
-            call("tvq_channel_sum", ptr(g2), M, N, 1, ptr(sink), 1, ptr(ws), stream_ptr())
-        return None
-    out = torch.empty(N, device=g2.device, dtype=torch.float32)
-    ws = torch.empty(value("tvq_channel_sum_workspace", M, N, 1), device=g2.device)
-    call("tvq_channel_sum", ptr(g2), M, N, 1, ptr(out), 0, ptr(ws), stream_ptr())
-    return out
+    out = sink if sink is not None else torch.empty(N, device=g2.device, dtype=torch.float32)
+    # into the flat gradient: off the critical path
+    with streams.offload(g2) if sink is not None else contextlib.nullcontext():
+        ws = torch.empty(value("tvq_channel_sum_workspace", M, N, 1), device=g2.device)
+        call("tvq_channel_sum", ptr(g2), M, N, 1, ptr(out), int(sink is not None), ptr(ws),
+             stream_ptr())
+    return None if sink is not None else out
 
 
 def weight_grad(g, x2, w_param, M, N, K, tag=None, b_param=None):
@@ -54,6 +54,18 @@ def weight_grad(g, x2, w_param, M, N, K, tag=None, b_param=None):
     return gemm(g, 1, N, x2, K, 1, N, K, M)
 
 
+def param_grads(g, x2, w, b, M, N, K, tag, need_w, need_b):
+    """(dW, db) of a Linear's parameters w, b (b may be None) from g (M x N) and its input x2
+    (M x K): both needed -> one grouped record (weight_grad with b), else each alone.  A
+    gradient that is not needed, or went into its flat-gradient view, is None."""
+    need_b = need_b and b is not None
+    if need_w and need_b:
+        return weight_grad(g, x2, w, M, N, K, tag, b)
+    dw = weight_grad(g, x2, w, M, N, K, tag) if need_w else None
+    db = _bias_grad_rows(g, grad_sink(b)) if need_b else None
+    return dw, db
+
+
 def scale_by(x, s):
     """x * s[0] (s: a one-element device tensor) in one kernel."""
     x = x.contiguous()
@@ -74,7 +86,7 @@ class _Linear(torch.autograd.Function):
         R = residual.reshape(M, N).contiguous() if residual is not None else None
         y = gemm(x2, K, 1, w, 1, K, M, N, K, bias=b, R=R, ldr=N, gate=gate)
         ctx.save_for_backward(x2, w)
-        ctx.has = (b is not None, residual is not None)
+        ctx.has_res = residual is not None
         ctx.shp = shp
         ctx.params = (w, b)
         ctx.wg_tag = wgrad.current_tag()
@@ -86,20 +98,14 @@ class _Linear(torch.autograd.Function):
         x2, w = ctx.saved_tensors
         M, K = x2.shape
         N = w.shape[0]
-        dres = gy if ctx.has[1] and ctx.needs_input_grad[3] else None
+        dres = gy if ctx.has_res and ctx.needs_input_grad[3] else None
         # gated branch (layer dropout): the branch's gradient is gate * gy
         g = scale_by(gy, ctx.gate) if ctx.gate is not None else gy
         g = g.reshape(M, N).contiguous()
-        dx = dw = db = None
+        dx = None
         if ctx.needs_input_grad[0]:
             dx = gemm(g, N, 1, w, K, 1, M, K, N).reshape(ctx.shp)
-        if ctx.needs_input_grad[1] and ctx.has[0] and ctx.needs_input_grad[2]:
-            dw, db = weight_grad(g, x2, ctx.params[0], M, N, K, ctx.wg_tag, ctx.params[1])
-        else:
-            if ctx.needs_input_grad[1]:
-                dw = weight_grad(g, x2, ctx.params[0], M, N, K, ctx.wg_tag)
-            if ctx.has[0] and ctx.needs_input_grad[2]:
-                db = _bias_grad_rows(g, grad_sink(ctx.params[1]))
+        dw, db = param_grads(g, x2, *ctx.params, M, N, K, ctx.wg_tag, *ctx.needs_input_grad[1:3])
         return dx, dw, db, dres, None
 
 
@@ -125,16 +131,10 @@ class _LinearSelfRes(torch.autograd.Function):
         x2, w = ctx.saved_tensors
         M, K = x2.shape
         g = gy.reshape(M, K).contiguous()
-        dx = dw = db = None
+        dx = None
         if ctx.needs_input_grad[0]:
             dx = gemm(g, K, 1, w.contiguous(), K, 1, M, K, K, R=g, ldr=K).reshape(ctx.shp)
-        if ctx.needs_input_grad[1] and ctx.params[1] is not None and ctx.needs_input_grad[2]:
-            dw, db = weight_grad(g, x2, ctx.params[0], M, K, K, ctx.wg_tag, ctx.params[1])
-        else:
-            if ctx.needs_input_grad[1]:
-                dw = weight_grad(g, x2, ctx.params[0], M, K, K, ctx.wg_tag)
-            if ctx.params[1] is not None and ctx.needs_input_grad[2]:
-                db = _bias_grad_rows(g, grad_sink(ctx.params[1]))
+        dw, db = param_grads(g, x2, *ctx.params, M, K, K, ctx.wg_tag, *ctx.needs_input_grad[1:3])
         return dx, dw, db
 
 
@@ -167,18 +167,16 @@ class _WeightProduct(torch.autograd.Function):
         M, K = w1.shape
         N = w2.shape[1]
         g = g.contiguous()
-        out = [None, None]
+        d1 = d2 = None
         if ctx.needs_input_grad[0]:
-            sk = grad_sink(ctx.params[0])
-            d = sk if sk is not None else torch.empty_like(w1)
-            gemm(g, N, 1, w2, 1, N, M, K, N, out=d, ldc=K, accumulate=sk is not None)
-            out[0] = None if sk is not None else d
+            d1, direct = grad_buffer(ctx.params[0])
+            gemm(g, N, 1, w2, 1, N, M, K, N, out=d1, ldc=K, accumulate=direct)
+            d1 = None if direct else d1
         if ctx.needs_input_grad[1]:
-            sk = grad_sink(ctx.params[1])
-            d = sk if sk is not None else torch.empty_like(w2)
-            gemm(w1, 1, K, g, N, 1, K, N, M, out=d, ldc=N, accumulate=sk is not None)
-            out[1] = None if sk is not None else d
-        return out[0], out[1]
+            d2, direct = grad_buffer(ctx.params[1])
+            gemm(w1, 1, K, g, N, 1, K, N, M, out=d2, ldc=N, accumulate=direct)
+            d2 = None if direct else d2
+        return d1, d2
 
 
 def weight_product(w1, w2):

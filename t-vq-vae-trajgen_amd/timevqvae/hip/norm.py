@@ -1,7 +1,7 @@
 """BatchNorm (+ fused SnakeActivation) and standalone Snake on the HIP path."""
 import torch
 
-from ._native import call, grad_sink, ptr, stream_ptr, value
+from ._native import call, grad_buffer, grad_buffers, ptr, stream_ptr, value
 from .conv import PackCache, _Conv2d
 
 
@@ -25,7 +25,6 @@ class _BNSnakeTrain(torch.autograd.Function):
              ptr(running_var), ptr(nbt), float(momentum), float(eps), ptr(a), ptr(y),
              ptr(save[:C]), ptr(save[C:2 * C]), ptr(save[2 * C:]), ptr(ws), stream_ptr())
         ctx.save_for_backward(x, w, a, save)
-        ctx.has = (w is not None, b is not None, a is not None)
         return y
 
     @staticmethod
@@ -49,7 +48,6 @@ class _BNSnakeTrainPart(torch.autograd.Function):
              ptr(running_mean), ptr(running_var), ptr(nbt), float(momentum), float(eps), ptr(a),
              ptr(y), ptr(save[:C]), ptr(save[C:2 * C]), ptr(save[2 * C:]), stream_ptr())
         ctx.save_for_backward(x, w, a, save)
-        ctx.has = (w is not None, b is not None, a is not None)
         return y
 
     @staticmethod
@@ -74,23 +72,13 @@ def _bn_snake_bwd(ctx, gy):
     dev = x.device
     g = gy.contiguous()
     dx = torch.empty_like(x)
-    has_w, has_b, has_a = ctx.has
-    sinks = [grad_sink(p) if h else None for p, h in zip(ctx.params, ctx.has)]
-    direct = all((s is not None) == h for s, h in zip(sinks, ctx.has))
-    if direct:
-        dw, db, da = sinks
-    else:
-        dw = torch.empty(C, device=dev) if has_w else None
-        db = torch.empty(C, device=dev) if has_b else None
-        da = torch.empty(C, device=dev) if has_a else None
+    (dw, db, da), direct = grad_buffers(ctx.params)
     ws = torch.empty(value("tvq_bn_workspace", B, C, HW), device=dev, dtype=torch.uint8)
     call("tvq_bn_bwd", ptr(g), ptr(x), B, C, HW, ptr(w), ptr(a), ptr(save[:C]),
          ptr(save[C:2 * C]), ptr(save[2 * C:]), ptr(dx), ptr(dw), ptr(db), ptr(da), int(direct),
          ptr(ws), stream_ptr())
     if direct:
         return dx, None, None, None, None, None, None, None, None
-    if da is not None:
-        da = da.view_as(ctx.params[2])
     return dx, dw, db, da, None, None, None, None, None
 
 
@@ -175,12 +163,11 @@ def _snake_bwd(ctx, gy, g_add):
     if g_add is not None and (g_add.shape != x.shape or not g_add.is_contiguous()):
         g_add = g_add.contiguous().view_as(x)
     dx = torch.empty_like(x)
-    sink = grad_sink(ctx.a_param)
-    da = sink if sink is not None else torch.empty(C, device=x.device)
+    da, direct = grad_buffer(ctx.a_param)
     ws = torch.empty(value("tvq_snake_workspace", B, C, HW), device=x.device, dtype=torch.uint8)
     call("tvq_snake_bwd", ptr(g), ptr(x), B, C, HW, ptr(a), ptr(g_add), ptr(dx), ptr(da),
-         int(sink is not None), ptr(ws), stream_ptr())
-    return dx, (None if sink is not None else da.view_as(ctx.a_param))
+         int(direct), ptr(ws), stream_ptr())
+    return dx, (None if direct else da)
 
 
 class _SnakeSkip(torch.autograd.Function):

@@ -13,7 +13,7 @@ import os
 import torch
 
 from . import rng
-from ._native import call, grad_sink, ptr, stream_ptr, value
+from ._native import call, grad_buffers, ptr, stream_ptr, value
 from .conv import _immediate, _keep
 
 ENABLED = True
@@ -43,8 +43,7 @@ class _ResBlockTrain(torch.autograd.Function):
         h = torch.empty(value("tvq_resblock_saved_floats", B, C, H, W), device=x.device)
         y = torch.empty_like(x)
         save = torch.empty(4 * C, device=x.device, dtype=torch.float32)
-        seed = rng.seed_tensor(x.device) if drop_p > 0 else None
-        off = rng.call_offset(site) if drop_p > 0 else 0
+        seed, off = rng.draw(x.device, site, drop_p > 0)
         call("tvq_resblock_train_fwd", ptr(x), B, C, H, W, ptr(a1), ptr(w1), ptr(b1), ptr(bn_w),
              ptr(bn_b), ptr(rmean), ptr(rvar), ptr(nbt), float(momentum), float(eps), ptr(a2),
              ptr(w2), ptr(b2), float(drop_p), ptr(seed), off, ptr(h), ptr(y), ptr(save),
@@ -60,17 +59,9 @@ class _ResBlockTrain(torch.autograd.Function):
         x, h, save = ctx.saved_tensors
         a1, w1, b1, bn_w, bn_b, a2, w2, b2 = ctx.params
         B, C, H, W = x.shape
-        dev = x.device
         g = gy.contiguous()
         dx = torch.empty_like(x)
-        params = ctx.params
-        has = [p is not None for p in params]
-        sinks = [grad_sink(p) if p is not None else None for p in params]
-        direct = all((s is not None) == hh for s, hh in zip(sinks, has))
-        if direct:
-            grads = sinks
-        else:
-            grads = [torch.empty(p.shape, device=dev) if p is not None else None for p in params]
+        grads, direct = grad_buffers(ctx.params)
         da1, dw1, db1, dbw, dbb, da2, dw2, db2 = grads
         ws = _ws(x)
         drop_p, off = ctx.drop
@@ -138,10 +129,9 @@ class _ResBlockPairTrain(torch.autograd.Function):
         y2 = torch.empty_like(x)
         save1 = torch.empty(4 * C, device=x.device)
         save2 = torch.empty(4 * C, device=x.device)
-        seed = rng.seed_tensor(x.device) if drop_p > 0 else None
         # the offsets the two blocks draw in this order when run one by one
-        off1 = rng.call_offset(site1) if drop_p > 0 else 0
-        off2 = rng.call_offset(site2) if drop_p > 0 else 0
+        seed, off1 = rng.draw(x.device, site1, drop_p > 0)
+        off2 = rng.draw(x.device, site2, drop_p > 0)[1]
         keep = [_arr(p1), _arr(p2), _arr([rm1, rv1]), _arr([rm2, rv2])]
         ws1, ws2 = _ws(x), _ws(x)
         call("tvq_resblock_pair_train_fwd", ptr(x), B, C, H, W, *keep, ptr(nbt1), ptr(nbt2),
@@ -158,18 +148,10 @@ class _ResBlockPairTrain(torch.autograd.Function):
         x, h1, y1, save1, h2, save2 = ctx.saved_tensors
         p1, p2 = ctx.params
         B, C, H, W = x.shape
-        dev = x.device
         g = gy.contiguous()
         dx = torch.empty_like(x)
         dy1 = torch.empty_like(x)
-        params = tuple(p1) + tuple(p2)
-        has = [p is not None for p in params]
-        sinks = [grad_sink(p) if p is not None else None for p in params]
-        direct = all((s is not None) == hh for s, hh in zip(sinks, has))
-        if direct:
-            grads = sinks
-        else:
-            grads = [torch.empty(p.shape, device=dev) if p is not None else None for p in params]
+        grads, direct = grad_buffers(tuple(p1) + tuple(p2))
         ws1, ws2 = _ws(x), _ws(x)
         drop_p, off1, off2 = ctx.drop
 
@@ -232,8 +214,7 @@ class _ResBlockProjTrain(torch.autograd.Function):
         h = torch.empty(value("tvq_resblock_proj_saved_floats", B, Ci, Co, H, W), device=x.device)
         y = torch.empty((B, Co, H, W), device=x.device)
         save = torch.empty(4 * Co, device=x.device, dtype=torch.float32)
-        seed = rng.seed_tensor(x.device) if drop_p > 0 else None
-        off = rng.call_offset(site) if drop_p > 0 else 0
+        seed, off = rng.draw(x.device, site, drop_p > 0)
         call("tvq_resblock_proj_train_fwd", ptr(x), B, Ci, Co, H, W, ptr(a1), ptr(w1), ptr(b1),
              ptr(bn_w), ptr(bn_b), ptr(rmean), ptr(rvar), ptr(nbt), float(momentum), float(eps),
              ptr(a2), ptr(w2), ptr(b2), ptr(wp), ptr(bp), float(drop_p), ptr(seed), off, ptr(h),
@@ -250,17 +231,9 @@ class _ResBlockProjTrain(torch.autograd.Function):
         a1, w1, b1, bn_w, bn_b, a2, w2, b2, wp, bp = ctx.params
         B, Ci, H, W = x.shape
         Co = w1.shape[0]
-        dev = x.device
         g = gy.contiguous()
         dx = torch.empty_like(x)
-        params = ctx.params
-        has = [p is not None for p in params]
-        sinks = [grad_sink(p) if p is not None else None for p in params]
-        direct = all((s is not None) == hh for s, hh in zip(sinks, has))
-        if direct:
-            grads = sinks
-        else:
-            grads = [torch.empty(p.shape, device=dev) if p is not None else None for p in params]
+        grads, direct = grad_buffers(ctx.params)
         da1, dw1, db1, dbw, dbb, da2, dw2, db2, dwp, dbp = grads
         ws = _pws(x, Co)
         drop_p, off = ctx.drop

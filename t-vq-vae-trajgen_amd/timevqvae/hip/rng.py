@@ -42,6 +42,15 @@ def seed_tensor(device) -> torch.Tensor:
     return t
 
 
+def draw(device, site: int, on=True):
+    """(seed tensor, offset) of one random draw at `site`.  `on` false (dropout p = 0, noise
+    injected by a test): (None, 0), and the call index does not advance, so the draws that
+    follow keep their offsets."""
+    if not on:
+        return None, 0
+    return seed_tensor(device), call_offset(site)
+
+
 def manual_seed(seed: int):
     """Seed the dropout stream and restart site numbering, so a model constructed after
     this call draws the same masks as any other model constructed the same way."""

@@ -39,8 +39,7 @@ def maskgit_sample(logits, s, mask_id, gumbel=None, site=0):
     s = s.contiguous()
     sampled = torch.empty_like(s)
     selp = torch.empty((B, n), device=logits.device, dtype=torch.float32)
-    seed = rng.seed_tensor(logits.device) if gumbel is None else None
-    off = rng.call_offset(site) if gumbel is None else 0
+    seed, off = rng.draw(logits.device, site, gumbel is None)
     call("tvq_maskgit_sample", ptr(logits), sb, sn, B, n, K, ptr(s), int(mask_id),
          ptr(gumbel.contiguous() if gumbel is not None else None), ptr(seed), off, ptr(sampled),
          ptr(selp), stream_ptr())
@@ -75,8 +74,7 @@ def _tied_logits_sample(h, h_null, cfg_scale, W, bias, K, s, mask_id, gumbel, si
     sampled = torch.empty_like(s)
     selp = torch.empty((B, n), device=dev, dtype=torch.float32)
     logits = torch.empty((B, n, K), device=dev, dtype=torch.float32) if want_logits else None
-    seed = rng.seed_tensor(dev) if gumbel is None else None
-    off = rng.call_offset(site) if gumbel is None else 0
+    seed, off = rng.draw(dev, site, gumbel is None)
     shape = (M, D, ptr(W.contiguous()), K, ptr(bias), nb, bias.stride(0))
     guide = () if h_null is None else (float(cfg_scale),)
     call("tvq_tied_logits_sample" if h_null is None else "tvq_tied_logits_sample_cfg",
@@ -116,8 +114,7 @@ def maskgit_remask(selp, k, temperature, sampled=None, mask_id=0, u_gumbel=None,
     dev = selp.device
     s_out = torch.empty_like(sampled) if sampled is not None else None
     masking = torch.empty((B, n), device=dev, dtype=torch.uint8) if want_masking else None
-    seed = rng.seed_tensor(dev) if u_gumbel is None else None
-    off = rng.call_offset(site) if u_gumbel is None else 0
+    seed, off = rng.draw(dev, site, u_gumbel is None)
     call("tvq_maskgit_remask", ptr(selp.contiguous()), B, n, int(k), float(temperature),
          ptr(u_gumbel.contiguous() if u_gumbel is not None else None), ptr(seed), off,
          ptr(sampled), int(mask_id), ptr(s_out), ptr(masking), stream_ptr())

@@ -205,12 +205,9 @@ def vq_codebook_pass(x, embed, cluster_size, embed_avg, *, straight_through, ema
     # also writes x token-major so that those sums read contiguous rows
     rows = (torch.empty((M, D), device=dev, dtype=torch.float32)
             if ema and straight_through and sD != 1 else None)
-    seed, off = None, 0
-    if svq_temp:
-        if gumbel is not None and (gumbel.shape != (M, K) or not gumbel.is_contiguous()):
-            raise ValueError("vq: injected gumbel noise must be a contiguous (M, K) tensor")
-        seed = rng.seed_tensor(dev) if gumbel is None else None
-        off = rng.call_offset(_SVQ_SITE) if gumbel is None else 0
+    if svq_temp and gumbel is not None and (gumbel.shape != (M, K) or not gumbel.is_contiguous()):
+        raise ValueError("vq: injected gumbel noise must be a contiguous (M, K) tensor")
+    seed, off = rng.draw(dev, _SVQ_SITE, bool(svq_temp) and gumbel is None)
     call("tvq_vq_assign_rows", ptr(x), B, N, D, sB, sN, sD, ptr(embed), ptr(ee), K,
          int(bool(straight_through)), float(svq_temp or 0.0), ptr(gumbel), ptr(seed), off,
          ptr(out), ptr(idx), ptr(idx32), ptr(partial), ptr(rows), s)

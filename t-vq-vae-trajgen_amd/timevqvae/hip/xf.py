@@ -6,9 +6,9 @@ import os
 import torch
 
 from . import rng, streams, wgrad
-from ._native import call, grad_sink, ptr, stream_ptr, value
+from ._native import call, grad_buffer, grad_buffers, grad_sink, ptr, stream_ptr, value
 from .conv import _keep
-from .linear import _bias_grad_rows, gemm, weight_grad
+from .linear import gemm, param_grads, weight_grad
 
 
 def _rows(x):
@@ -36,13 +36,12 @@ def _rmsnorm_bwd(ctx, gy, gr):
     dy = gy.reshape(M, D).contiguous()
     dres = gr.reshape(M, D).contiguous() if gr is not None else None
     dx = torch.empty_like(x2)
-    sink = grad_sink(ctx.g_param)
-    dg = sink if sink is not None else torch.empty(D, device=x2.device)
+    dg, direct = grad_buffer(ctx.g_param)
     ws = torch.empty(value("tvq_norm_bwd_workspace", M, D), device=x2.device)
     call("tvq_rmsnorm_bwd", ptr(dy), ptr(x2), M, D, ptr(g), float(ctx.scale), ptr(inv),
-         ptr(dres), ptr(dx), ptr(dg), int(sink is not None), ptr(ws), stream_ptr())
+         ptr(dres), ptr(dx), ptr(dg), int(direct), ptr(ws), stream_ptr())
     _keep(ws)  # its reduction may be deferred (hip.conv.wgrad_deferred)
-    return dx.reshape(ctx.shape), (None if sink is not None else dg), None
+    return dx.reshape(ctx.shape), (None if direct else dg), None
 
 
 class _RMSNorm(torch.autograd.Function):
@@ -95,7 +94,6 @@ class _LayerNorm(torch.autograd.Function):
              ptr(mean), ptr(rstd), stream_ptr())
         ctx.save_for_backward(x2, gamma, mean, rstd)
         ctx.params = (gamma, beta)
-        ctx.has = (gamma is not None, beta is not None)
         ctx.shape = x.shape
         return y.reshape(x.shape)
 
@@ -105,13 +103,7 @@ class _LayerNorm(torch.autograd.Function):
         M, D = x2.shape
         dy = gy.reshape(M, D).contiguous()
         dx = torch.empty_like(x2)
-        sinks = [grad_sink(p) if h else None for p, h in zip(ctx.params, ctx.has)]
-        direct = all((s is not None) == h for s, h in zip(sinks, ctx.has))
-        if direct:
-            dg, db = sinks
-        else:
-            dg = torch.empty(D, device=x2.device) if ctx.has[0] else None
-            db = torch.empty(D, device=x2.device) if ctx.has[1] else None
+        (dg, db), direct = grad_buffers(ctx.params)
         ws = torch.empty(value("tvq_norm_bwd_workspace", M, D), device=x2.device)
         call("tvq_layernorm_bwd", ptr(dy), ptr(x2), M, D, ptr(gamma), ptr(mean), ptr(rstd), ptr(dx),
              ptr(dg), ptr(db), int(direct), ptr(ws), stream_ptr())
@@ -142,7 +134,6 @@ class _LinearAct(torch.autograd.Function):
         ctx.params = (w, b)
         ctx.wg_tag = wgrad.current_tag()
         ctx.act = act
-        ctx.has_b = b is not None
         ctx.shape = x.shape
         return y.reshape(*x.shape[:-1], N)
 
@@ -156,16 +147,10 @@ class _LinearAct(torch.autograd.Function):
             gp = torch.empty_like(g)
             call("tvq_gelu_bwd", ptr(g), ptr(pre), g.numel(), ptr(gp), stream_ptr())
             g = gp
-        dx = dw = db = None
+        dx = None
         if ctx.needs_input_grad[0]:
             dx = gemm(g, N, 1, w, K, 1, M, K, N).reshape(ctx.shape)
-        if ctx.needs_input_grad[1] and ctx.has_b and ctx.needs_input_grad[2]:
-            dw, db = weight_grad(g, x2, ctx.params[0], M, N, K, ctx.wg_tag, ctx.params[1])
-        else:
-            if ctx.needs_input_grad[1]:
-                dw = weight_grad(g, x2, ctx.params[0], M, N, K, ctx.wg_tag)
-            if ctx.has_b and ctx.needs_input_grad[2]:
-                db = _bias_grad_rows(g, grad_sink(ctx.params[1]))
+        dw, db = param_grads(g, x2, *ctx.params, M, N, K, ctx.wg_tag, *ctx.needs_input_grad[1:3])
         return dx, dw, db, None
 
 
@@ -193,8 +178,7 @@ class _FusedFF(torch.autograd.Function):
         r2 = r.reshape(-1, 128).contiguous()
         M = x2.shape[0]
         y, pre, hd = (torch.empty_like(x2) for _ in range(3))
-        seed = rng.seed_tensor(xn.device) if p > 0 else None
-        off = rng.call_offset(site) if p > 0 else 0
+        seed, off = rng.draw(xn.device, site, p > 0)
         call("tvq_ffn_fwd", ptr(x2), ptr(r2), M, 128, ptr(w1), ptr(b1), ptr(w2), ptr(b2),
              ptr(gate), float(p), ptr(seed), off, ptr(y), ptr(pre), ptr(hd), stream_ptr())
         ctx.save_for_backward(x2, pre, hd, w1, w2)
@@ -217,17 +201,8 @@ class _FusedFF(torch.autograd.Function):
              ptr(ctx.seed), off, ptr(d_pre), ptr(dxn), ptr(gg), stream_ptr())
         W1p, b1p, W2p, b2p = ctx.params
         g2w = gg if gg is not None else g2
-        dw1 = db1 = dw2 = db2 = None
-        if need[4] and need[5]:  # weight and bias gradients in one grouped record
-            dw2, db2 = weight_grad(g2w, hd, W2p, M, 128, 128, ctx.wg_tag, b2p)
-        else:
-            dw2 = weight_grad(g2w, hd, W2p, M, 128, 128, ctx.wg_tag) if need[4] else None
-            db2 = _bias_grad_rows(g2w, grad_sink(b2p)) if need[5] else None
-        if need[2] and need[3]:
-            dw1, db1 = weight_grad(d_pre, x2, W1p, M, 128, 128, ctx.wg_tag, b1p)
-        else:
-            dw1 = weight_grad(d_pre, x2, W1p, M, 128, 128, ctx.wg_tag) if need[2] else None
-            db1 = _bias_grad_rows(d_pre, grad_sink(b1p)) if need[3] else None
+        dw2, db2 = param_grads(g2w, hd, W2p, b2p, M, 128, 128, ctx.wg_tag, need[4], need[5])
+        dw1, db1 = param_grads(d_pre, x2, W1p, b1p, M, 128, 128, ctx.wg_tag, need[2], need[3])
         return (dxn.reshape(shp) if need[0] else None, gy if need[1] else None, dw1, db1, dw2,
                 db2, None, None, None)
 
@@ -272,16 +247,13 @@ class _AttnBranch(torch.autograd.Function):
         B, S, D = x.shape
         M = B * S
         x2 = x.reshape(M, D).contiguous()
-        W = _stacked([wq, wk, wv], (3 * D, D))
-        if W is None:
-            W = torch.cat([wq, wk, wv], 0).contiguous()
+        W = _qkv_weight(wq, wk, wv, (3 * D, D))
         dev = x.device
         y, xn, o = (torch.empty_like(x2) for _ in range(3))
         inv = torch.empty(M, device=dev)
         qkv = torch.empty((M, 3 * D), device=dev)
         lse = torch.empty(B * heads * S, device=dev)
-        seed = rng.seed_tensor(dev) if p > 0 else None
-        off = rng.call_offset(site) if p > 0 else 0
+        seed, off = rng.draw(dev, site, p > 0)
         call("tvq_attn_branch_fwd", ptr(x2), B, S, D, heads, ptr(g), math.sqrt(D), ptr(W), ptr(wo),
              ptr(gate), float(p), ptr(seed), off, ptr(y), ptr(xn), ptr(inv), ptr(qkv), ptr(o),
              ptr(lse), stream_ptr())
@@ -304,27 +276,17 @@ class _AttnBranch(torch.autograd.Function):
         dx = torch.empty_like(x2)
         dqkv = torch.empty((M, L), device=dev)
         gg = torch.empty_like(g2) if ctx.gate is not None else None
-        sink_g = grad_sink(g)
-        dg = sink_g if sink_g is not None else torch.empty(D, device=dev)
+        dg, direct = grad_buffer(g)
         ws = torch.empty(value("tvq_attn_branch_workspace", B, D), device=dev)
         call("tvq_attn_branch_bwd", ptr(g2), ptr(x2), B, S, D, heads, ptr(g), math.sqrt(D), ptr(inv),
              ptr(W), ptr(wo), ptr(ctx.gate), p, ptr(ctx.seed), off, ptr(qkv), ptr(o), ptr(lse),
-             ptr(dx), ptr(dqkv), ptr(gg), ptr(dg), int(sink_g is not None), ptr(ws), stream_ptr())
+             ptr(dx), ptr(dqkv), ptr(gg), ptr(dg), int(direct), ptr(ws), stream_ptr())
         _keep(ws)  # its gain-gradient reduction may be deferred
         dws = [None, None, None]
         if any(need[2:5]):
-            sinks = [grad_sink(w) for w in (wq, wk, wv)]
-            sink = _stacked(sinks, (L, D)) if all(s_ is not None for s_ in sinks) else None
-            if sink is not None:  # into the flat gradient (stacked view)
-                if not wgrad.defer(dqkv, L, xn, D, sink, D, L, D, M, ctx.wg_tag):
-                    with streams.offload(dqkv, xn):
-                        gemm(dqkv, 1, L, xn, D, 1, L, D, M, out=sink, ldc=D, accumulate=True)
-            else:
-                dW = gemm(dqkv, 1, L, xn, D, 1, L, D, M)
-                dws = [dW[i * D:(i + 1) * D] for i in range(3)]
+            dws = _qkv_weight_grad(dqkv, xn, (wq, wk, wv), L, D, M, ctx.wg_tag)
         dwo = weight_grad(gg if gg is not None else g2, o, wo, M, D, D, ctx.wg_tag) if need[5] else None
-        return (dx.reshape(B, S, D), None if sink_g is not None else dg, *dws, dwo, None, None, None,
-                None)
+        return (dx.reshape(B, S, D), None if direct else dg, *dws, dwo, None, None, None, None)
 
 
 def attn_branch_supported(x, g, attn):
@@ -334,8 +296,7 @@ def attn_branch_supported(x, g, attn):
             and attn.heads == 2):
         return False
     ws = (g, attn.to_q.weight, attn.to_k.weight, attn.to_v.weight, attn.to_out.weight)
-    return all(w.dtype == torch.float32 and w.is_cuda and w.is_contiguous() and
-               w.data_ptr() % 16 == 0 for w in ws) and tuple(attn.to_q.weight.shape) == (128, 128)
+    return all(_param16(w) for w in ws) and tuple(attn.to_q.weight.shape) == (128, 128)
 
 
 def attn_branch(x, g, attn, gate, p):
@@ -354,8 +315,7 @@ class _Attention(torch.autograd.Function):
         q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
         o = torch.empty_like(q)
         lse = torch.empty(B * heads * S, device=q.device)
-        seed = rng.seed_tensor(q.device) if drop_p > 0 else None
-        off = rng.call_offset(site) if drop_p > 0 else 0
+        seed, off = rng.draw(q.device, site, drop_p > 0)
         scale = Dh ** -0.5
         call("tvq_attention_fwd", ptr(q), HD, ptr(k), HD, ptr(v), HD, ptr(o), HD, ptr(lse), B,
              heads, S, Dh, float(scale), float(drop_p), ptr(seed), off, stream_ptr())
@@ -398,6 +358,27 @@ def _stacked(ws, shape):
     return torch.as_strided(p0, shape, (shape[1], 1))
 
 
+def _qkv_weight(wq, wk, wv, shape):
+    """[Wq; Wk; Wv] row-stacked: the view of the flat parameters when adjacent, else a copy."""
+    W = _stacked([wq, wk, wv], shape)
+    return W if W is not None else torch.cat([wq, wk, wv], 0).contiguous()
+
+
+def _qkv_weight_grad(dqkv, xn, params, L, D, M, tag):
+    """[dWq, dWk, dWv] = the row thirds of dqkv^T xn (L x D; dqkv M x L, xn M x D) in one GEMM:
+    into the stacked flat-gradient view of `params` when there is one (grouped at the
+    backward's end inside a wgrad.grouped() scope) and then None each, else returned."""
+    sinks = [grad_sink(p) for p in params]
+    sink = _stacked(sinks, (L, D)) if all(s is not None for s in sinks) else None
+    if sink is None:
+        dW = gemm(dqkv, 1, L, xn, D, 1, L, D, M)
+        return [dW[i * (L // 3):(i + 1) * (L // 3)] for i in range(3)]
+    if not wgrad.defer(dqkv, L, xn, D, sink, D, L, D, M, tag):
+        with streams.offload(dqkv, xn):
+            gemm(dqkv, 1, L, xn, D, 1, L, D, M, out=sink, ldc=D, accumulate=True)
+    return [None, None, None]
+
+
 class _QKVAttention(torch.autograd.Function):
     """o = attention(x Wq^T, x Wk^T, x Wv^T): the three projections as ONE GEMM against the
     row-stacked [Wq; Wk; Wv] (a view of the flat parameters when they are adjacent), the
@@ -412,15 +393,12 @@ class _QKVAttention(torch.autograd.Function):
         HD = wq.shape[0]
         x2 = x.reshape(B * S, D).contiguous()
         M = B * S
-        W = _stacked([wq, wk, wv], (3 * HD, D))
-        if W is None:
-            W = torch.cat([wq, wk, wv], 0).contiguous()
+        W = _qkv_weight(wq, wk, wv, (3 * HD, D))
         qkv = gemm(x2, D, 1, W, 1, D, M, 3 * HD, D)
         Dh = HD // heads
         o = torch.empty((M, HD), device=x.device)
         lse = torch.empty(B * heads * S, device=x.device)
-        seed = rng.seed_tensor(x.device) if drop_p > 0 else None
-        off = rng.call_offset(site) if drop_p > 0 else 0
+        seed, off = rng.draw(x.device, site, drop_p > 0)
         scale = Dh ** -0.5
         L = 3 * HD
         call("tvq_attention_fwd", ptr(qkv), L, ptr(qkv[:, HD:]), L, ptr(qkv[:, 2 * HD:]), L, ptr(o),
@@ -449,15 +427,7 @@ class _QKVAttention(torch.autograd.Function):
             dx = gemm(dqkv, L, 1, W, D, 1, M, D, L).reshape(B, S, D)
         dws = [None, None, None]
         if any(ctx.needs_input_grad[1:4]):
-            sinks = [grad_sink(p) for p in ctx.params]
-            sink = _stacked(sinks, (L, D)) if all(s is not None for s in sinks) else None
-            if sink is not None:  # into the flat gradient (stacked view)
-                if not wgrad.defer(dqkv, L, x2, D, sink, D, L, D, M, ctx.wg_tag):  # else grouped later
-                    with streams.offload(dqkv, x2):
-                        gemm(dqkv, 1, L, x2, D, 1, L, D, M, out=sink, ldc=D, accumulate=True)
-            else:
-                dW = gemm(dqkv, 1, L, x2, D, 1, L, D, M)
-                dws = [dW[i * HD:(i + 1) * HD] for i in range(3)]
+            dws = _qkv_weight_grad(dqkv, x2, ctx.params, L, D, M, ctx.wg_tag)
         return (dx, *dws, None, None, None)
 
 
@@ -474,8 +444,7 @@ class _Embedding(torch.autograd.Function):
         M = idx.numel()
         V, D = table.shape
         out = torch.empty((M, D), device=table.device)
-        seed = rng.seed_tensor(table.device) if drop_p > 0 else None
-        off = rng.call_offset(site) if drop_p > 0 else 0
+        seed, off = rng.draw(table.device, site, drop_p > 0)
         call("tvq_embedding_fwd", ptr(idx), M, D, ptr(table), ptr(out), D, int(mask_id),
              float(drop_p), ptr(seed), off, stream_ptr())
         ctx.save_for_backward(idx)
@@ -490,16 +459,14 @@ class _Embedding(torch.autograd.Function):
         V, D, mask_id, drop_p, off = ctx.cfg
         M = idx.numel()
         g2 = g.reshape(M, D).contiguous()
-        sink = grad_sink(ctx.table)
+        tg, direct = grad_buffer(ctx.table)
         # into the flat gradient: aux stream (same one as the tied-logits table grad)
-        with (streams.offload(idx, g2) if sink is not None else contextlib.nullcontext()):
-            tg = sink if sink is not None else torch.empty((V, D), device=g.device)
+        with (streams.offload(idx, g2) if direct else contextlib.nullcontext()):
             ws = torch.empty(value("tvq_embedding_bwd_workspace", M, V), device=g.device,
                              dtype=torch.int32)
-            call("tvq_embedding_bwd", ptr(idx), M, D, ptr(g2), D, V, ptr(tg),
-                 int(sink is not None), int(mask_id), float(drop_p), ptr(ctx.seed), off, ptr(ws),
-                 stream_ptr())
-        return None, (None if sink is not None else tg), None, None, None
+            call("tvq_embedding_bwd", ptr(idx), M, D, ptr(g2), D, V, ptr(tg), int(direct),
+                 int(mask_id), float(drop_p), ptr(ctx.seed), off, ptr(ws), stream_ptr())
+        return None, (None if direct else tg), None, None, None
 
 
 def embedding(idx, table, mask_id=-1, drop_p=0.0, site=0):
@@ -539,13 +506,10 @@ class _EmbedAssemble(torch.autograd.Function):
         dt1 = torch.empty_strided(sh1, st1, device=dev) if need[1] else None
         dt2 = torch.empty_strided(m2[0], m2[1], device=dev) if (m2 is not None and need[2]) else None
         s2 = m2[1] if m2 is not None else (0, 0, 0)
-        sink = grad_sink(ctx.pos_w) if need[3] else None
-        dpos = None
-        if need[3]:
-            dpos = sink if sink is not None else torch.zeros_like(ctx.pos_w)
+        dpos, direct = grad_buffer(ctx.pos_w, zeros=True) if need[3] else (None, False)
         call("tvq_embed_assemble_bwd", ptr(g), B, n, D1, D2, ptr(dcls), ptr(dt1), *st1, ptr(dt2),
-             *s2, ptr(dpos), int(sink is not None), stream_ptr())
-        return dcls, dt1, dt2, (None if sink is not None else dpos), None
+             *s2, ptr(dpos), int(direct), stream_ptr())
+        return dcls, dt1, dt2, (None if direct else dpos), None
 
 
 def embed_assemble(cls_emb, t1, t2, pos_w, n):
@@ -707,8 +671,7 @@ def prior_lf_eval_supported(tf, s):
             return False
     # tvq_prior_lf_eval reads every weight with 16-byte loads (TVQ_CHECK_ARG there): a
     # FusedAdamW flat buffer packs parameters without padding, so check, don't assume
-    return all(p.dtype == torch.float32 and p.is_cuda and p.is_contiguous() and
-               p.data_ptr() % 16 == 0 for p in tf.parameters())
+    return all(_param16(p) for p in tf.parameters())
 
 
 def _prior_lf_args(tf, s, class_idx, ws=None):
@@ -772,8 +735,7 @@ def prior_lf_eval_sample(tf, s, class_idx, mask_id, gumbel=None, site=0, want_lo
     sampled = torch.empty((B, n), device=dev, dtype=torch.int64)
     selp = torch.empty((B, n), device=dev, dtype=torch.float32)
     logits = torch.empty((B, n, K), device=dev, dtype=torch.float32) if want_logits else None
-    seed = rng.seed_tensor(dev) if gumbel is None else None
-    off = rng.call_offset(site) if gumbel is None else 0
+    seed, off = rng.draw(dev, site, gumbel is None)
     head = (ptr(s), B, n, s.stride(0), ptr(cls), tf.n_classes, 128, arr, depth, K,
             float(tf.pred_head[2].eps))
     tail = (int(mask_id), ptr(gumbel.contiguous() if gumbel is not None else None), ptr(seed),

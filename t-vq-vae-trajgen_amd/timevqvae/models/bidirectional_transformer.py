@@ -500,8 +500,7 @@ class BidirectionalTransformer(nn.Module):
             u = self._class_rand
             rnd = (torch.as_tensor(u).to(device=device, dtype=torch.float32).reshape(-1).contiguous()
                    if u is not None else None)
-            seed = rng.seed_tensor(device) if rnd is None else None
-            off = rng.call_offset(self._site_l) if rnd is None else 0
+            seed, off = rng.draw(device, self._site_l, rnd is None)
             call("tvq_class_index", ptr(y), y.numel(), float(self.p_unconditional), self.n_classes,
                  ptr(seed), off, ptr(rnd), ptr(idx), stream_ptr())
             idx = idx.reshape(class_condition.shape)

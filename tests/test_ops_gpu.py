@@ -1,5 +1,8 @@
 """Per-kernel numerics: each HIP op vs the plain PyTorch fp32 CPU op (forward and
 backward).  Tolerance: rel-L2 <= 1e-5 (fp32 reassociation only), max-abs scaled."""
+import contextlib
+import functools
+
 import numpy as np
 import pytest
 import torch
@@ -387,6 +390,62 @@ def test_linear(M, K, N, res, cuda):
     close(od, oc, what="fwd")
     for i in range(len(shapes)):
         close(d[i].grad, c[i].grad, what=f"grad{i}")
+
+
+@functools.lru_cache(maxsize=None)
+def _param_grads_case():
+    """g (100, 70), x (100, 33) (test_linear's odd shape) and the fp64 g^T x, column sums of g."""
+    gen = torch.Generator().manual_seed(7033)
+    g, x = torch.randn(100, 70, generator=gen), torch.randn(100, 33, generator=gen)
+    return g, x, g.double().t() @ x.double(), g.double().sum(0)
+
+
+@pytest.mark.parametrize("grouped", [False, True])
+@pytest.mark.parametrize("flat", [False, True])
+@pytest.mark.parametrize("need_w,need_b", [(True, True), (True, False), (False, True)])
+def test_param_grads(need_w, need_b, flat, grouped, cuda):
+    """linear.param_grads, the one weight / bias gradient branch of every Linear-like Function:
+    dW = g^T x and db = the column sums of g against fp64, returned (plain parameters) or
+    summed into the FusedAdamW flat views (then None is returned), inside and outside a
+    wgrad.grouped() scope; a gradient that is not needed is None and its flat view keeps the
+    sentinel it held, bit for bit."""
+    from timevqvae.hip import streams, wgrad
+    from timevqvae.hip.linear import param_grads
+    from timevqvae.hip.optim import FusedAdamW
+    SENTINEL = -123.456
+    g, x, dw_ref, db_ref = _param_grads_case()
+    M, N, K = 100, 70, 33
+    g, x = g.to(cuda), x.to(cuda)
+    w = torch.zeros(N, K, device=cuda, requires_grad=True)
+    b = torch.zeros(N, device=cuda, requires_grad=True)
+    if flat:
+        opt = FusedAdamW([w, b])
+        assert w._tvq_flat and b._tvq_flat and not opt.flat_grad.any()
+        for p, need in ((w, need_w), (b, need_b)):
+            if not need:
+                p.grad.fill_(SENTINEL)
+    with (wgrad.grouped() if grouped else contextlib.nullcontext()):
+        dw, db = param_grads(g, x, w, b, M, N, K, None, need_w, need_b)
+    streams.join()
+    torch.cuda.synchronize()
+    for name, p, d, need, ref in (("dw", w, dw, need_w, dw_ref), ("db", b, db, need_b, db_ref)):
+        if flat:
+            assert d is None, name
+            if need:
+                close(p.grad, ref, what=name)
+            else:
+                assert torch.equal(p.grad, torch.full_like(p.grad, SENTINEL)), name
+        elif need:
+            assert p.grad is None
+            close(d, ref, what=name)
+        else:
+            assert d is None and p.grad is None, name
+    # b is None counts as need_b false
+    if not flat and not grouped and need_w:
+        dw, db = param_grads(g, x, w, None, M, N, K, None, True, need_b)
+        torch.cuda.synchronize()
+        assert db is None
+        close(dw, dw_ref, what="dw, no bias")
 
 
 @pytest.mark.parametrize("M,N,K", [(25600, 128, 128), (300, 512, 128), (97, 32, 256), (1000, 64, 32),
