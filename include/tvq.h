@@ -258,18 +258,15 @@ int tvq_conv_packcache_release(int64_t id);
 int tvq_conv_packcache_pause(int64_t on);
 int64_t tvq_conv_packcache_entries(void);
 
-/* Deferred weight-gradient reductions: between begin() and flush(stream), the split sums
- * of tvq_conv2d_wgrad / tvq_convT2d_wgrad (<= 256 splits) are recorded instead of launched,
- * and flush() runs them all in a few batched launches on `stream` -- bit for bit the same
- * sums.  Until the flush the callers' workspaces must stay allocated and dw / db are not
- * final.  Process-wide host state, one scope at a time. */
+/* Deferred weight-gradient reductions: between begin() and flush(), the split sums of
+ * tvq_conv2d_wgrad / tvq_convT2d_wgrad (<= 256 splits) and the RMSNorm / LayerNorm weight
+ * gradients accumulated into a flat gradient (tvq_rmsnorm_bwd / tvq_layernorm_bwd with
+ * accumulate = 1) are recorded instead of launched, each with the stream it was issued on,
+ * and flush() runs them in a few batched launches per such stream -- bit for bit the same
+ * sums (`stream` is not used).  Until the flush the callers' workspaces must stay allocated
+ * and the gradients are not final.  Process-wide host state, one scope at a time. */
 int tvq_conv_wgrad_defer_begin(void);
 int tvq_conv_wgrad_defer_flush(tvq_stream_t stream);
-/* The same scope, recording only the reductions issued on `stream` -- the conv weight
- * gradients and the RMSNorm / LayerNorm weight gradients accumulated into a flat gradient
- * (tvq_rmsnorm_bwd / tvq_layernorm_bwd with accumulate = 1); those issued on other streams
- * run at once.  Flush on the same `stream`. */
-int tvq_wgrad_defer_begin_stream(tvq_stream_t stream);
 /* paused != 0: calls inside the scope reduce immediately (a gradient needed at once) */
 int tvq_conv_wgrad_defer_pause(int64_t paused);
 /* op: 0 conv2d fwd, 1 convT2d fwd, 2 conv2d dgrad, 3 convT2d dgrad, 4 conv2d wgrad,

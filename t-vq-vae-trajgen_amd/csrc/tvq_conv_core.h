@@ -22,9 +22,15 @@
 //   tvq_conv_halo.hip   conv_halo / conv_small / conv_n16
 //   tvq_conv_s2.hip     conv_s2f / conv_s2t (+ fold), conv_wgrad_s2
 //   tvq_conv_s2m.hip    conv_s2m_t (+ fold): the same T gather at 32 / 64 reduction channels
-//   tvq_conv_wgrad.hip  the other weight gradients, their entry points, the deferred split
-//                       sums, tvq_channel_sum
 //   tvq_conv_pack.hip   weight packing and the pack cache
+// and the W form's, one per family as well:
+//   tvq_conv_wgrad.hip       ABI entry points, wgrad_ladder (the W dispatcher), conv_wgrad_ws,
+//                            conv_wgrad (the split GEMM that takes every shape)
+//   tvq_conv_wgrad_t32.hip   conv_wgrad_t32 (wide maps, 32x32x2 tile)
+//   tvq_conv_wgrad_w8.hip    conv_wgrad_w8 (narrow maps, image-batched, multi-problem)
+//   tvq_conv_wgrad_halo.hip  conv_wgrad_halo (one image's halo tile per step)
+//   (conv_wgrad_s2 lives in tvq_conv_s2.hip; the split sums every family ends in, and their
+//   deferral scope, are tvq_reduce.hip's conv_wgrad_finish)
 #pragma once
 #include "tvq_common.h"
 
@@ -286,7 +292,8 @@ static constexpr int HALO_LDS_MAX = 64 * 1024;
 #define PH_OF(KH) ((int)(KH) / 2)
 #define PW_OF(KW) (((int)(KW) - 1) / 2)
 
-// kind: 0 = 3x4 s2 (EncBlock / ConvT), 1 = 3x3 s1, 2 = 1x1, 3 = 1x3 s1 (Conv1d k3)
+// kind: 0 = 3x4 s2 (EncBlock / ConvT), 1 = 3x3 s1, 2 = 1x1, 3 = 1x3 s1 (Conv1d k3).  The W
+// launchers' dispatch, MACRO(KH, KW, SW, REPL); `kind` is a kind_of() value the entry point checked
 #define TVQ_DISPATCH_KIND(kind, repl, MACRO)                                  \
   switch (kind) {                                                             \
     case 0: if (repl) { MACRO(3, 4, 2, true) } else { MACRO(3, 4, 2, false) } break; \
@@ -295,7 +302,6 @@ static constexpr int HALO_LDS_MAX = 64 * 1024;
     case 3: if (repl) { MACRO(1, 3, 1, true) } else { MACRO(1, 3, 1, false) } break; \
     case 4: MACRO(1, 7, 1, false) break;                                      \
     case 5: MACRO(1, 4, 2, false) break;                                      \
-    default: set_error("conv: unsupported kernel kind %d", kind); return TVQ_ERR_ARG; \
   }
 
 static int kind_of(int KH, int KW, int SW) {
@@ -410,6 +416,50 @@ bool launch_tap(int mode, int kind, bool repl, const float* in, const float* wt,
 void launch_gemm_flat(int mode, int kind, bool repl, const float* in, const float* wt, float* out,
                       const ConvGeom& g, const Epi& e, hipStream_t st);
 int64_t conv_gemm_ws(const ConvGeom& g, int KK);  // floats: pack + split-K slab
+
+// ---- the weight-gradient (W form) families.  One problem: G (B, N, Hout, Wo) against In
+// (B, C, Hin, Win) into `slab`, S rows of [N][kcols] that conv_wgrad_finish sums in order;
+// kcols = C*KH*KW (+ 1: the bias column).  Each family has one plan function, which fixes its
+// split count S from the shape; its launcher and conv_wgrad_ws both take S from there.
+struct WgradArgs {
+  const float* G;
+  const float* in;
+  float* slab;
+  int B, C, Hin, Win, N, Hout, Wo;
+  int KH, KW, SW, kind;  // kind: the kind_of() value the entry point checked
+  bool repl;
+  int kcols;
+  hipStream_t st;
+};
+// floats of S slab rows [N][C*KK + 1]: the one place a split count becomes a size
+inline int64_t wgrad_slab_floats(int64_t S, int64_t N, int64_t C, int64_t KK) {
+  return S * N * (C * KK + 1);
+}
+// launch_wgrad_*: the launch's S, or 0 with nothing launched when the shape is not theirs
+
+// tvq_conv_wgrad_t32.hip
+struct WtSplit {
+  int S, spr;  // splits of the 32-position stages, stages per split
+};
+bool wt32_fits(int64_t B, int64_t C, int64_t H, int64_t Wi, int64_t N, int64_t Wo, int64_t KH,
+               int64_t KW, int64_t SW, int64_t replicate);
+WtSplit wt32_plan(int64_t B, int64_t C, int64_t H, int64_t W, int64_t N, int64_t KK);
+int launch_wgrad_t32(const WgradArgs& a);
+
+// tvq_conv_wgrad_w8.hip.  w8_splits: one slab row per block of images, 0 when the batch is
+// not whole blocks (the kernel's other conditions need the map, which conv_wgrad_ws is not given)
+int w8_splits(int64_t B);
+int launch_wgrad_w8(const WgradArgs& a);
+
+// tvq_conv_wgrad_halo.hip.  The blocking and S depend on (N, C, KK, B) alone.
+struct WHaloSplit {
+  int FN, CB;      // 16-row n tiles per block, input channels per block
+  int nblk, cblk;  // blocks over n and over c
+  int S, ips;      // splits over images, images per split
+};
+WHaloSplit whalo_split(int64_t N, int64_t C, int KK, int64_t B);
+int whalo_plane_stride(int hw, int KK, int KW, int WP, int SW, int CB);
+int launch_wgrad_halo(const WgradArgs& a);
 
 // tvq_conv_wgrad.hip: workspace floats of tvq_conv2d_wgrad / tvq_convT2d_wgrad
 int64_t conv_wgrad_ws(int64_t N, int64_t C, int64_t KH, int64_t KW, int64_t B, int64_t Hout,

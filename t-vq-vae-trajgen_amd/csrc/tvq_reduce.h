@@ -20,6 +20,17 @@ struct RrJob {
 };
 constexpr int RR_ONE_ROWS = 256;
 void reduce_rows_batch(const RrJob* jobs, int n, hipStream_t st);
+// Deterministic split sum of a weight-gradient slab slab[s][n][kcols] (s < splits) into
+// dw[n][kcols-1] (+ db[n] from the last column when db != null); batched into the open
+// tvq_conv_wgrad_defer scope when there is one.  reduce_rows_scratch(splits, N*kcols)
+// floats of scratch must follow the slab.
+void conv_wgrad_finish(float* slab, int splits, int64_t N, int64_t kcols, float* dw, float* db,
+                       int accumulate, hipStream_t st);
+// out[0..N) (+)= sum of P contiguous rows of `in` -- a parameter gradient the optimizer
+// alone reads (norm weights): batched into the open deferral scope when the scope takes
+// it, else reduce_rows now (scratch: reduce_rows_scratch(P, N) floats)
+void param_rows_finish(const float* in, int64_t P, int64_t N, float* out, int accumulate,
+                       float* scratch, hipStream_t st);
 // stable group-by of indices in [0,V): offsets[V+1], perm[M]; scratch: group_by_scratch_ints ints
 int64_t group_by_scratch_ints(int64_t M, int64_t V);
 // counts / countsf (optional, V each): the per-value counts as int32 and float

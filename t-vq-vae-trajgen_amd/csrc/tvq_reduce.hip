@@ -11,8 +11,14 @@
 //              permutation (positions grouped by value in increasing position
 //              order) -> segmented sums in a fixed order with no float atomics
 //              (VQ embed_sum, nn.Embedding backward).
+// chan_sum     out[c] (+)= sum over (b, p) of x[b, c, p] (tvq_channel_sum: bias and other
+//              per-channel parameter gradients), two stages in a fixed order.
+// deferral     conv_wgrad_finish / param_rows_finish: a slab's reduce_rows, or inside a
+//              tvq_conv_wgrad_defer_* scope a record that the flush runs in batched launches.
 #include "tvq_common.h"
 #include "tvq_reduce.h"
+
+#include <vector>
 
 namespace tvq {
 
@@ -741,6 +747,106 @@ int* group_by_seg_start(int* scratch, int64_t M, int64_t V) {
   return scratch + 2 * chunks * V;
 }
 
+// ---------------------------------------------------------------- channel sums
+// Per-channel sum over (B, HW) of a (B, C, HW) tensor: out[c] (+)= sum, deterministic.
+// Stage 1: partial[c][chunk], chunk = `ipc` whole images of channel c (contiguous HW rows,
+// float4 loads, 4 in flight per thread); stage 2 (fixed xor tree over <= 64 partials, one
+// load per lane) in the last block of channel c when `cnt` is given, else
+// chan_sum_final_kernel.
+__device__ __forceinline__ void chan_sum_final_one(const float* part, int chunks, int c,
+                                                   float* out, int accumulate) {
+  float s = 0.f;
+  for (int i = 0; i < chunks; ++i) s += ld_wt(part + (int64_t)c * chunks + i);
+  out[c] = accumulate ? out[c] + s : s;
+}
+__global__ __launch_bounds__(256) void chan_sum_partial_kernel(const float* __restrict__ x, int B,
+                                                               int C, int HW, int ipc, int chunks,
+                                                               int vec, float* __restrict__ part,
+                                                               int* __restrict__ cnt,
+                                                               float* __restrict__ out,
+                                                               int accumulate) {
+  __shared__ float red[4];
+  const int c = blockIdx.x, ch = blockIdx.y;
+  const int b0 = ch * ipc, b1 = min(B, b0 + ipc);
+  float s = 0.f;
+  if (vec) {
+    const int hw4 = HW >> 2, n4 = (b1 - b0) * hw4;
+    for (int i0 = threadIdx.x; i0 < n4; i0 += 256 * 4) {
+      floatx4 v[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int i = i0 + u * 256;
+        const int bb = b0 + (i < n4 ? i : 0) / hw4, q = (i < n4 ? i : 0) % hw4;
+        v[u] = *reinterpret_cast<const floatx4*>(x + ((int64_t)bb * C + c) * HW + 4 * q);
+      }
+#pragma unroll
+      for (int u = 0; u < 4; ++u)
+        if (i0 + u * 256 < n4) s += (v[u][0] + v[u][1]) + (v[u][2] + v[u][3]);
+    }
+  } else {
+    const int n = (b1 - b0) * HW;
+    for (int i = threadIdx.x; i < n; i += 256) {
+      const int bb = b0 + i / HW, p = i % HW;
+      s += x[((int64_t)bb * C + c) * HW + p];
+    }
+  }
+  s = block_sum(s, red);
+  if (threadIdx.x == 0) st_wt(part + (int64_t)c * chunks + ch, s);
+  if (cnt && last_block(cnt + c, chunks) && threadIdx.x < 64) {
+    float t = threadIdx.x < chunks ? ld_wt(part + (int64_t)c * chunks + threadIdx.x) : 0.f;
+    t = wave_sum(t);
+    if (threadIdx.x == 0) out[c] = accumulate ? out[c] + t : t;
+  }
+}
+__global__ void chan_sum_final_kernel(const float* __restrict__ part, int C, int chunks,
+                                      float* __restrict__ out, int accumulate) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= C) return;
+  chan_sum_final_one(part, chunks, c, out, accumulate);
+}
+
+// ---------------------------------------------------------------- deferral scope
+// Deferred weight-gradient split sums (tvq_conv_wgrad_defer_*): inside a scope the
+// slabs' reductions are recorded and run by a few batched launches at the flush instead
+// of one launch per conv (the caller keeps the workspaces alive until then).  Each record
+// carries the stream its producer ran on: the flush issues each stream's records as one
+// batch on that stream (ordered after that stream's producers), so a backward spread over
+// several streams (a branch's side stream) defers its reductions too.
+struct RdRec {
+  RrJob job;
+  hipStream_t st;
+};
+static std::vector<RdRec> g_rd;
+static bool g_rd_on = false, g_rd_paused = false;
+
+static bool rd_records(int64_t rows) {
+  return g_rd_on && !g_rd_paused && rows <= RR_ONE_ROWS;
+}
+
+void conv_wgrad_finish(float* slab, int splits, int64_t N, int64_t kcols, float* dw, float* db,
+                       int accumulate, hipStream_t st) {
+  // deterministic split sum; kcols = Kred+1 splits out the bias column.  The level-1
+  // scratch follows the slab in the workspace.
+  const int64_t L = kcols > 0 && db ? kcols : 0;
+  if (rd_records(splits)) {  // the single-level case: batched at the flush
+    g_rd.push_back({{slab, dw, db, splits, N * kcols, L, accumulate}, st});
+    return;
+  }
+  reduce_rows(slab, splits, N * kcols, N * kcols, dw, db, L, accumulate,
+              slab + (int64_t)splits * N * kcols, st);
+}
+
+// out[0..N) (+)= sum of the P contiguous rows of `in` (a parameter gradient only the
+// optimizer reads): joins the open deferral scope's batch, else reduce_rows now
+void param_rows_finish(const float* in, int64_t P, int64_t N, float* out, int accumulate,
+                       float* scratch, hipStream_t st) {
+  if (rd_records(P)) {
+    g_rd.push_back({{in, out, nullptr, P, N, 0, accumulate}, st});
+    return;
+  }
+  reduce_rows(in, P, N, N, out, nullptr, 0, accumulate, scratch, st);
+}
+
 }  // namespace tvq
 
 using namespace tvq;
@@ -755,4 +861,80 @@ extern "C" int tvq_reduce_rows(const float* in, int64_t P, int64_t N, int64_t ld
   TVQ_CHECK_ARG(reduce_rows_scratch(P, N) == 0 || workspace, "tvq_reduce_rows: needs workspace");
   reduce_rows(in, P, N, ld, out, nullptr, 0, (int)accumulate, workspace, (hipStream_t)stream);
   return launch_status("tvq_reduce_rows");
+}
+
+extern "C" int tvq_conv_wgrad_defer_begin(void) {
+  TVQ_CHECK_ARG(!g_rd_on, "tvq_conv_wgrad_defer_begin: a scope is already open");
+  g_rd.clear();
+  g_rd_on = true;
+  return TVQ_OK;
+}
+
+extern "C" int tvq_conv_wgrad_defer_pause(int64_t paused) {
+  g_rd_paused = paused != 0;
+  return TVQ_OK;
+}
+
+extern "C" int tvq_conv_wgrad_defer_flush(tvq_stream_t stream) {
+  g_rd_on = false;
+  g_rd_paused = false;
+  // one batch per producing stream, in first-record order ((void)stream: kept for the ABI)
+  (void)stream;
+  std::vector<RrJob> jobs;
+  while (!g_rd.empty()) {
+    const hipStream_t st = g_rd.front().st;
+    jobs.clear();
+    std::vector<RdRec> rest;
+    int64_t bytes = 0;
+    for (const RdRec& r : g_rd) {
+      if (r.st == st) {
+        jobs.push_back(r.job);
+        bytes += r.job.P * r.job.N * 4;
+        TVQ_PLAN("wgrad_flush_job st=%p P=%lld N=%lld", (void*)st, (long long)r.job.P,
+                 (long long)r.job.N);
+      } else {
+        rest.push_back(r);
+      }
+    }
+    TVQ_PLAN("wgrad_flush st=%p jobs=%d MB=%.1f", (void*)st, (int)jobs.size(), bytes / 1e6);
+    reduce_rows_batch(jobs.data(), (int)jobs.size(), st);
+    g_rd.swap(rest);
+  }
+  return launch_status("tvq_conv_wgrad_defer_flush");
+}
+
+extern "C" int64_t tvq_channel_sum_workspace(int64_t B, int64_t C, int64_t HW) {
+  if (HW == 1) {
+    const int64_t r = reduce_rows_scratch(B, C);
+    return r > 0 ? r : 1;
+  }
+  int64_t chunks = (B * HW + 8191) / 8192;
+  if (chunks > 64) chunks = 64;
+  if (chunks < 1) chunks = 1;
+  return C * chunks;
+}
+
+// out[c] (+)= sum_{b,p} x[b,c,p]   (bias gradients), deterministic
+extern "C" int tvq_channel_sum(const float* x, int64_t B, int64_t C, int64_t HW, float* out,
+                               int64_t accumulate, float* workspace, tvq_stream_t stream) {
+  TVQ_CHECK_ARG(x && out && workspace && B > 0 && C > 0 && HW > 0, "tvq_channel_sum: bad args");
+  if (HW == 1) {  // row-major (B, C): coalesced column sums
+    reduce_rows(x, B, C, C, out, nullptr, 0, (int)accumulate, workspace, (hipStream_t)stream);
+    return launch_status("tvq_channel_sum");
+  }
+  const int64_t chunks = tvq_channel_sum_workspace(B, C, HW) / C;
+  hipStream_t st = (hipStream_t)stream;
+  int* cnt = counters(C, FIN_REDUCE);
+  // whole images per chunk (at most the workspace's `chunks`, which is <= 64)
+  const int64_t ipc = (B + chunks - 1) / chunks;
+  const int64_t nch = (B + ipc - 1) / ipc;
+  TVQ_CHECK_ARG(ipc * HW < (1ll << 31), "tvq_channel_sum: bad geometry");
+  const int vec = (HW & 3) == 0 && ((uintptr_t)x & 15) == 0;
+  hipLaunchKernelGGL(chan_sum_partial_kernel, dim3((int)C, (int)nch), dim3(256), 0, st, x,
+                     (int)B, (int)C, (int)HW, (int)ipc, (int)nch, vec, workspace, cnt, out,
+                     (int)accumulate);
+  if (!cnt)
+    hipLaunchKernelGGL(chan_sum_final_kernel, dim3((int)((C + 127) / 128)), dim3(128), 0, st,
+                       workspace, (int)C, (int)nch, out, (int)accumulate);
+  return launch_status("tvq_channel_sum");
 }

@@ -107,7 +107,7 @@ struct RB {
   static constexpr int K1OFF = 2 * PLANE + PANEL + PARTCW;
   static constexpr int CONSTP = 2 * PS;  // ones plane + zeros plane
   // external weight gradients (C = 32 at W = 16): the backward kernels write the conv
-  // operands (g and s planes) and conv_wgrad_w16_multi reduces them over images in one
+  // operands (g and s planes) and conv_wgrad_w8_multi reduces them over images in one
   // launch per ResBlock (pair), instead of a C x (9C + 1) slab row per image (37 KB, 12x the
   // image's activations); taken when RBArgs::wext is set (B % 16 == 0)
   static constexpr bool WEXT = C_ == 32 && W_ == 16;
@@ -124,7 +124,7 @@ struct RBArgs {  // every pointer / scalar a fused ResBlock kernel reads or writ
   float *h_out, *y, *du, *dx, *slab1, *slab2, *slabda, *slabda2;
   // RB::WEXT shapes with wext set: the (B, C, 3, W) conv operand planes the backward writes
   // (conv1: g = dh, s = Snake_a1(x); conv2: g = Dropout'(dy), s = Snake_a2(BN(h))) and the
-  // small slabs conv_wgrad_w16_multi reduces them into
+  // small slabs conv_wgrad_w8_multi reduces them into
   float *gp1, *sp1, *gp2, *sp2, *wsl1, *wsl2;
   int wext;
   double* part;
@@ -1044,10 +1044,10 @@ static bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 // the external-weight-gradient form (RB::WEXT) for this shape and batch
 static bool rb_wext(int64_t B, int64_t C, int64_t W) {
-  if (!(C == 32 && W == 16) || !conv_wgrad_w16_fits(B, C, C)) return false;
+  if (!(C == 32 && W == 16) || !conv_wgrad_w8_fits(16, B, C, C)) return false;
   // the g / s planes and the small slab fit in the per-image slab region they replace
   const int64_t pl = B * C * 3 * W;
-  return 2 * pl + conv_wgrad_w16_slab_floats(B, C, C) <= B * C * (9 * C + 1);
+  return 2 * pl + conv_wgrad_w8_slab_floats(16, B, C, C) <= B * C * (9 * C + 1);
 }
 
 static RBArgs rb_fwd_args(const float* x, int64_t B, int64_t C, int64_t W, const float* a1,
@@ -1111,7 +1111,7 @@ static void rb_bwd_finish(const RBArgs& a, int64_t C, float* da1, float* dw1, fl
     float* ws[2] = {a.wsl2, a.wsl1};
     float* dw[2] = {dw2, dw1};
     float* db[2] = {db2, db1};
-    conv_wgrad_w16_multi(2, x, dy, ws, dw, db, a.B, C, C, a.accumulate, st);
+    conv_wgrad_w8_multi(16, 2, x, dy, ws, dw, db, a.B, C, C, a.accumulate, st);
   } else {
     conv_wgrad_finish(a.slab2, a.B, C, kc, dw2, db2, a.accumulate, st);
     conv_wgrad_finish(a.slab1, a.B, C, kc, dw1, db1, a.accumulate, st);
@@ -1134,7 +1134,7 @@ static void rb_bwd_finish_pair(const RBArgs& b2, const RBArgs& b1, int64_t C, fl
   float* ws[4] = {b2.wsl2, b2.wsl1, b1.wsl2, b1.wsl1};
   float* dw[4] = {g2[6], g2[1], g1[6], g1[1]};
   float* db[4] = {g2[7], g2[2], g1[7], g1[2]};
-  conv_wgrad_w16_multi(4, x, dy, ws, dw, db, b2.B, C, C, b2.accumulate, st);
+  conv_wgrad_w8_multi(16, 4, x, dy, ws, dw, db, b2.B, C, C, b2.accumulate, st);
   conv_wgrad_finish(b2.slabda, b2.B, C, 1, g2[0], nullptr, b2.accumulate, st);
   conv_wgrad_finish(b2.slabda2, b2.B, C, 1, g2[5], nullptr, b2.accumulate, st);
   conv_wgrad_finish(b1.slabda, b1.B, C, 1, g1[0], nullptr, b1.accumulate, st);

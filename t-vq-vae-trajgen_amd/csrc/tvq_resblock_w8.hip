@@ -226,7 +226,7 @@ int w8_pair_bwd(const float* dy, const float* x, int64_t B, const float* const* 
   if (rc) return rc;
   const Bwd* bs[2] = {&b2, &b1};
   float* const* gs[2] = {g2, g1};
-  if (conv_wgrad_w8_fits(B, C, C)) {  // the pair's four weight gradients in one launch
+  if (conv_wgrad_w8_fits(W, B, C, C)) {  // the pair's four weight gradients in one launch
     const float* xs[4];
     const float* dys[4];
     float* wsl[4];
@@ -239,7 +239,7 @@ int w8_pair_bwd(const float* dy, const float* x, int64_t B, const float* const* 
       xs[2 * i + 1] = b.s1; dys[2 * i + 1] = b.dh; wsl[2 * i + 1] = b.wg1;  // conv1: (s1, dh)
       dw[2 * i + 1] = gs[i][1]; db[2 * i + 1] = gs[i][2];
     }
-    conv_wgrad_w8_multi(4, xs, dys, wsl, dw, db, B, C, C, (int)accumulate, st);
+    conv_wgrad_w8_multi(W, 4, xs, dys, wsl, dw, db, B, C, C, (int)accumulate, st);
     for (int i = 0; i < 2; ++i) da1_finish(*bs[i], C, gs[i][0], accumulate, st);
     return launch_status("tvq_resblock_pair_bwd");
   }

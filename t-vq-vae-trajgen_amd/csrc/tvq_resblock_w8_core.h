@@ -677,9 +677,15 @@ static Bwd bwd_args(int64_t Ci, int64_t Co, const float* dy, const float* x, con
 static int wgrad_3x3(const Bwd& b, int64_t Ci, int64_t Co, float* const* g, int64_t accumulate,
                      hipStream_t st) {
   const int64_t B = b.a.B;
-  if (Ci == Co && conv_wgrad_w8_pair(b.s2, b.g2, b.wg2, g[6], g[7], b.s1, b.dh, b.wg1, g[1], g[2],
-                                     B, Ci, Co, (int)accumulate, st))
+  if (Ci == Co && conv_wgrad_w8_fits(W, B, Ci, Co)) {
+    const float* const x[2] = {b.s2, b.s1};
+    const float* const dy[2] = {b.g2, b.dh};
+    float* const ws[2] = {b.wg2, b.wg1};
+    float* const dw[2] = {g[6], g[1]};
+    float* const db[2] = {g[7], g[2]};
+    conv_wgrad_w8_multi(W, 2, x, dy, ws, dw, db, B, Ci, Co, (int)accumulate, st);
     return TVQ_OK;
+  }
   const int rc = tvq_conv2d_wgrad(b.s2, B, Co, 3, W, b.g2, Co, W, 3, 3, 1, 0, g[6], g[7],
                                   accumulate, b.wg2, st);
   if (rc) return rc;

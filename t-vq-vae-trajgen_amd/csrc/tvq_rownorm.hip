@@ -26,7 +26,6 @@
 #include <math.h>
 
 #include "tvq_common.h"
-#include "tvq_conv_internal.h"
 #include "tvq_reduce.h"
 
 namespace tvq {

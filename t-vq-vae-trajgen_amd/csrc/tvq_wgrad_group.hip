@@ -398,7 +398,7 @@ __host__ __device__ constexpr int wg_kc(int tw) { return tw == 1 ? 16 : 8; }
 // Plans are made per launch: a launch holds one tile class (wide 128 x 64 = 4, 64 x 64 = 2,
 // 32 x 32 = 1) and at most WG_MAXD descriptors, in the caller's order.  Its split count S
 // is chosen from the launch's work units (64 x 64 tiles for classes 4 and 2, 32 x 32 for
-// class 1) so that it has about TVQ_WG_UNITS (default 1000, resp. 1024) unit-splits: the
+// class 1) so that it has about 1000, resp. 1024, unit-splits (wg_splits): the
 // LF prior's 16 Linears + its head (100 units) get S = 10, i.e. 500 wide blocks, one round
 // at 2 per CU; a lone 256 x 256 Linear gets short spans over many blocks.  Every
 // descriptor of the launch uses S (its k span: K / S rounded up to whole chunks of the 4

@@ -33,7 +33,6 @@
 #include <math.h>
 
 #include "tvq_common.h"
-#include "tvq_conv_internal.h"
 #include "tvq_ff.h"
 #include "tvq_reduce.h"
 

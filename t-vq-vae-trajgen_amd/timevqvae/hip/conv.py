@@ -41,21 +41,17 @@ DEFER_WGRAD = True  # False (tests): every weight-gradient split sum at once
 
 @contextlib.contextmanager
 def wgrad_deferred(this_stream_only=False):
-    """Inside the scope the conv weight-gradient split sums are recorded and run by a few
-    batched launches on the current stream at the exit (tvq_conv_wgrad_defer_*), bit for
-    bit the same sums, instead of one reduction launch per conv.  Wrap a backward pass;
-    gradients are final only after the exit.  this_stream_only: record only the reductions
-    issued on the current stream -- conv weight gradients and the norm weight gradients
-    accumulated into a flat gradient (a backward that runs on several streams); the others
-    run at once."""
+    """Inside the scope the conv weight-gradient split sums, and the norm weight gradients
+    accumulated into a flat gradient, are recorded with the stream they were issued on and
+    run at the exit by a few batched launches on each such stream (tvq_conv_wgrad_defer_*),
+    bit for bit the same sums, instead of one reduction launch each.  Wrap a backward pass;
+    gradients are final only after the exit.  this_stream_only is accepted for its callers
+    and changes nothing: a backward that runs on several streams defers on all of them."""
     global _defer_keep
     if _defer_keep is not None or not DEFER_WGRAD:
         yield  # nested (the outer scope flushes) or switched off
         return
-    if this_stream_only:
-        call("tvq_wgrad_defer_begin_stream", stream_ptr())
-    else:
-        call("tvq_conv_wgrad_defer_begin")
+    call("tvq_conv_wgrad_defer_begin")
     _defer_keep = []
     try:
         yield

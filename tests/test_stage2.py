@@ -256,7 +256,7 @@ def test_deferred_norm_and_conv_reductions_bitwise(kind, cuda):
     """The prior's backward into a flat gradient (FusedAdamW) inside
     wgrad_deferred(this_stream_only=True) -- the RMSNorm / LayerNorm gain gradients and the
     Upscale conv weight gradients join one batched reduction at the scope's exit
-    (tvq_wgrad_defer_begin_stream) -- gives bit for bit the gradients of the immediate
+    (tvq_conv_wgrad_defer_begin) -- gives bit for bit the gradients of the immediate
     reductions."""
     from timevqvae.hip.conv import wgrad_deferred
     from timevqvae.hip.optim import FusedAdamW
