@@ -6,11 +6,15 @@ and central moments on the device) and the `Metrics` class (reference evaluation
 for the ROCKET extractor, and the flyability evaluation's trajectory distances (reference
 evaluation/flyability_eval.py calculate_trajectory_distances and flyability_utils/
 trajectory_distances; all 14, the continuous Frechet distance included, on the device).  The
-supervised FCN feature extractor, and with it the Inception Score of a trained classifier, is
-out of scope, as are the flyability evaluation's simulation, filtering and plotting
-(DESIGN.md)."""
+supervised FCN extractor (reference models/fcn.py) is in through `load_pretrained_FCN`,
+`fcn_features`, `fcn_class_probabilities` and `fcn_inception_score` (fcn_metrics.py; the
+eval forward on the device); the string paths (`Metrics(..., "supervised_fcn")`, the sampler's
+evaluation half, `.inception_score`) still refuse, and FCN training is out of scope, as are
+the flyability evaluation's simulation, filtering and plotting."""
 from .eval_utils import (calculate_fid, calculate_inception_score, feature_moments,
                          fid_device)
+from .fcn_metrics import (fcn_class_probabilities, fcn_features, fcn_inception_score,
+                          load_pretrained_FCN)
 from .flyability_eval import calculate_trajectory_distances
 from .flyability_utils import trajectory_distances_device
 from .metrics import Metrics
@@ -22,7 +26,8 @@ from .stat_metrics import (StatMetrics, auto_correlation_difference, kurtosis_di
 
 __all__ = ["DeviceKernels", "Metrics", "StatMetrics", "apply_kernel", "apply_kernels",
            "apply_kernels_device", "auto_correlation_difference", "calculate_fid",
-           "calculate_inception_score", "calculate_trajectory_distances", "feature_moments",
-           "fid_device", "generate_kernels",
-           "kurtosis_difference", "marginal_distribution_difference", "skewness_difference",
+           "calculate_inception_score", "calculate_trajectory_distances",
+           "fcn_class_probabilities", "fcn_features", "fcn_inception_score", "feature_moments",
+           "fid_device", "generate_kernels", "kurtosis_difference", "load_pretrained_FCN",
+           "marginal_distribution_difference", "skewness_difference",
            "stat_metrics_device", "trajectory_distances_device"]

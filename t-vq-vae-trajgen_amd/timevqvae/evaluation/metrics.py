@@ -7,8 +7,9 @@ transform (`apply_kernels_device`), the cast and the normalisation stay on the d
 leaves it once, as float32 numpy.  FID runs `calculate_fid` (device moments) after the
 reference's `remove_outliers`; the statistics run timevqvae.evaluation.stat_metrics.
 
-The supervised FCN extractor and the Inception Score need the pretrained FCN, which is out of
-scope here: both raise NotImplementedError."""
+The supervised FCN extractor and the Inception Score are not wired into this class: both
+raise NotImplementedError and name the functions of fcn_metrics.py that compute them
+(DESIGN.md)."""
 from typing import Tuple, Union
 
 import numpy as np
@@ -22,8 +23,9 @@ from .eval_utils import calculate_fid
 from .rocket_functions import DeviceKernels, apply_kernels_device, generate_kernels
 from .stat_metrics import stat_metrics_device
 
-FCN_OUT_OF_SCOPE = ("the supervised FCN feature extractor and the Inception Score need the "
-                    "pretrained FCN, which is out of scope here (DESIGN.md, Out of scope); use "
+FCN_OUT_OF_SCOPE = ("the supervised FCN feature extractor and the Inception Score are not wired "
+                    "into this path (DESIGN.md, Out of scope): use timevqvae.evaluation."
+                    "load_pretrained_FCN with fcn_features / fcn_inception_score, or "
                     "feature_extractor_type='rocket'")
 
 

@@ -10,7 +10,8 @@ feature extractor: `rocket_kernels`, `ts_len`, `n_classes`, `z_train`, `z_test`,
 loops `compute_z`, `compute_z_rec`, `compute_z_svq`, `compute_z_gen` (the reference's batch
 loop; ROCKET transform and float64 normalisation on the device), `fid_score` and
 `stat_metrics` (timevqvae.evaluation).  The supervised FCN extractor and `inception_score`
-need the pretrained FCN, which is out of scope (DESIGN.md), and raise NotImplementedError;
+are not wired into this class (timevqvae.evaluation.fcn_features / fcn_inception_score compute
+them; DESIGN.md) and raise NotImplementedError;
 PCA, t-SNE and the log_* plots are not reproduced."""
 from typing import Tuple, Union
 

@@ -1,12 +1,13 @@
-"""ctypes binding of libtvq_hip.so (include/tvq.h).
+"""ctypes binding of libtvq_hip.so (include/tvq.h and include/tvq_fcn.h).
 
 The library is loaded after `import torch` so that its NEEDED libamdhip64.so.7
 resolves to the HIP runtime torch already mapped (same soname): the kernels
 share torch's device context and streams.  There is no fallback: if the
 library is missing or no GPU is present, the first call raises.
 
-include/tvq.h is the single source of the signatures: SIGNATURES is parsed from it at
-import (`parse_header`), and a declaration the parser cannot map raises there.
+The headers are the single source of the signatures: SIGNATURES is parsed from include/tvq.h
+and EXTRA_SIGNATURES from include/tvq_fcn.h at import (`parse_header`), and a declaration the
+parser cannot map raises there.
 """
 import ctypes
 import os
@@ -24,15 +25,17 @@ _lock = threading.Lock()
 
 CSRC = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "csrc")
 HEADER = os.path.join(CSRC, "..", "..", "include", "tvq.h")
+FCN_HEADER = os.path.join(CSRC, "..", "..", "include", "tvq_fcn.h")
 
 
 def source_hash():
     """The stamp csrc/Makefile compiles into the library (tvq_source_hash): sha1 of every
-    csrc *.hip / *.h sorted by name, then include/tvq.h, first 16 hex digits."""
+    csrc *.hip / *.h sorted by name, then include/tvq.h and include/tvq_fcn.h, first 16 hex
+    digits."""
     import hashlib
     h = hashlib.sha1()
     names = sorted(n for n in os.listdir(CSRC) if n.endswith((".hip", ".h")))
-    for n in [os.path.join(CSRC, n) for n in names] + [HEADER]:
+    for n in [os.path.join(CSRC, n) for n in names] + [HEADER, FCN_HEADER]:
         with open(n, "rb") as f:
             h.update(f.read())
     return h.hexdigest()[:16]
@@ -99,6 +102,8 @@ def parse_header(text, origin="tvq.h"):
 
 with open(HEADER) as _f:
     SIGNATURES = parse_header(_f.read(), HEADER)  # name -> (argtypes, restype)
+with open(FCN_HEADER) as _f:  # the second public header; SIGNATURES stays tvq.h's table
+    EXTRA_SIGNATURES = parse_header(_f.read(), FCN_HEADER)
 
 
 class NativeError(RuntimeError):
@@ -118,7 +123,7 @@ def lib():
                 f"libtvq_hip.so not found at {LIB_PATH}; build it with "
                 "`python -c 'import __graft_entry__ as g; g.build()'` (no CPU fallback exists)")
         h = ctypes.CDLL(LIB_PATH)
-        for name, (args, res) in SIGNATURES.items():
+        for name, (args, res) in list(SIGNATURES.items()) + list(EXTRA_SIGNATURES.items()):
             fn = getattr(h, name)
             fn.argtypes = args
             fn.restype = res

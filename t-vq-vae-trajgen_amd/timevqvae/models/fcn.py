@@ -1,0 +1,44 @@
+"""FCNBaseline -- the reference's supervised feature extractor (models/fcn.py, from
+arXiv:1909.04939 via okrasolar/pytorch-timeseries) as a parameter holder with the reference's
+state-dict keys, its eval forward on the HIP path (timevqvae.hip.fcn).
+
+ConvBlock(in, 128, 8) -> ConvBlock(128, 256, 5) -> ConvBlock(256, 128, 3) -> mean over
+positions -> Linear(128, classes); every conv is TensorFlow-"same" padded, stride 1.  Training
+(BatchNorm batch statistics, the backward) is not on the HIP path: train with the reference's
+train_fcn and load the state dict.
+"""
+import torch
+from torch import nn
+
+from ..hip import fcn as ops
+
+
+class ConvBlock(nn.Module):
+    """Conv1d ("same" padding) -> BatchNorm1d -> ReLU; `layers.0` / `layers.1` hold the
+    parameters (fcn.py:42-62), the arithmetic is one tvq_fcn_conv_bn_relu launch."""
+
+    def __init__(self, in_channels: int, out_channels: int, kernel_size: int, stride: int) -> None:
+        super().__init__()
+        assert stride == 1, "the HIP path has the FCN's stride-1 blocks only"
+        self.layers = nn.Sequential(
+            nn.Conv1d(in_channels, out_channels, kernel_size, stride=stride),
+            nn.BatchNorm1d(num_features=out_channels),
+            nn.ReLU(),
+        )
+
+
+class FCNBaseline(nn.Module):
+    def __init__(self, in_channels: int, num_pred_classes: int = 1) -> None:
+        super().__init__()
+        self.input_args = {"in_channels": in_channels, "num_pred_classes": num_pred_classes}
+        self.layers = nn.Sequential(
+            ConvBlock(in_channels, 128, 8, 1),
+            ConvBlock(128, 256, 5, 1),
+            ConvBlock(256, 128, 3, 1),
+        )
+        self.final = nn.Linear(128, num_pred_classes)
+
+    def forward(self, x: torch.Tensor, return_feature_vector: bool = False) -> torch.Tensor:
+        """x (b, c, l) -> logits (b, classes), or the (b, 128) pooled features.  Eval mode
+        only (training mode raises NotImplementedError), under no_grad, input cast to fp32."""
+        return ops.fcn_forward(self, x, return_feature_vector)

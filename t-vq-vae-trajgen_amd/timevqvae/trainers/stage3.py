@@ -74,13 +74,15 @@ class Stage3(nn.Module):
         feature_fn(X (n, c, l) float64) -> Z (n, d) overrides the
         extractor.  Without it the extractor follows feature_extractor_type as the reference's
         Metrics.extract_feature_representations does (metrics.py:107-127): 'rocket' uses the
-        kernels drawn at construction; 'supervised_fcn' needs the pretrained FCN, which is
-        not on this path, so it raises instead of silently using another feature space."""
+        kernels drawn at construction; 'supervised_fcn' needs the pretrained FCN, which this
+        class does not load, so it raises instead of silently using another feature space:
+        pass feature_fn=lambda X: timevqvae.evaluation.fcn_features(fcn, X, batch_size)."""
         if feature_fn is None:
             if self.feature_extractor_type != "rocket":
                 raise NotImplementedError(
                     "search_optimal_tau with feature_extractor_type='supervised_fcn' needs the "
-                    "pretrained FCN extractor (not on the HIP path): pass feature_fn, or build "
+                    "pretrained FCN extractor: pass feature_fn (timevqvae.evaluation.fcn_features "
+                    "of a load_pretrained_FCN module), or build "
                     "Stage3 with feature_extractor_type='rocket'")
             feature_fn = self._rocket_fn
         maskgit = self.maskgit.to(device)
