@@ -6,38 +6,16 @@
 // pads (K-1)/2 on both sides and has neither a ReLU nor a pooled epilogue, so this is its
 // own implicit GEMM.
 //
-//   fcn_conv_kernel<K, WY, WG>   one core for the three layers.  A block of 4 waves owns a
-//     (64 output channels x 128 positions) tile of one sample: wave (wco, wpos) holds two
-//     32x32 accumulators of v_mfma_f32_32x32x2_f32, rows = channels 32 wco.., columns =
-//     positions 64 wpos + 32 p...  The reduction runs over chunks of FC_CC = 8 input channels
-//     (Ci padded with zeros), inside a chunk over the flat index r = ci K + k in steps of 2:
-//     lane half h supplies r = 2 s + h.
-//       A (weights)  read from the packed form of fcn_pack_kernel, one coalesced dword per
-//                    lane and step, straight into registers; the next chunk's are in flight
-//                    while this chunk multiplies.
-//       B (input)    the chunk's rows with their K-1 halo, zeros outside [0, L), staged
-//                    through two LDS buffers (next chunk's global loads in registers during
-//                    the MFMAs; one barrier per chunk).  A half-wave reads 32 consecutive
-//                    floats: no bank conflict.
-//     Every output is one k-ordered fmaf chain over r ascending, so it does not depend on
-//     the batch or the grid.  Epilogue: relu(fma(scale, acc, shift)).  WY: y is stored.  WG:
-//     the block walks all position tiles of its sample (gridDim.y == 1); a lane adds its
-//     column's values tile after tile, then the 32 columns are added by a fixed xor tree and
-//     the two position halves through LDS: an order that depends on L only.
+//   fcn_conv_kernel   tvq_fcn_core.h, the core shared with the training kernels; here its
+//     FC_EP_EVAL epilogue with the reference's left padding (K-1)/2.
 //   fcn_head_kernel   one wave per row: logits by a lane-strided dot and a fixed xor tree,
 //     softmax with the row maximum subtracted over the wave's LDS copy of the logits.
 #include "../../include/tvq_fcn.h"
 #include "tvq_common.h"
+#include "tvq_fcn_core.h"
 
 namespace tvq {
 namespace {
-
-constexpr int FC_T = 256;              // threads per block: 2 (channels) x 2 (positions) waves
-constexpr int FC_CC = 8;               // input channels per chunk
-constexpr int FC_TL = 128;             // positions per block tile
-constexpr int FC_ROW = FC_TL + 8;      // LDS row: tile + halo of up to 7
-constexpr int FC_COT = 64;             // output channels per block
-constexpr int FC_MAXK = 8;
 
 __global__ __launch_bounds__(256) void fcn_pack_kernel(const float* __restrict__ w,
                                                        float* __restrict__ wp, int Co, int Ci,
@@ -54,137 +32,6 @@ __global__ __launch_bounds__(256) void fcn_pack_kernel(const float* __restrict__
   wp[e] = ci < Ci ? w[((int64_t)co * Ci + ci) * K + k] : 0.f;
 }
 
-template <int K, bool WY, bool WG>
-__global__ __launch_bounds__(FC_T, 2) void fcn_conv_kernel(
-    const float* __restrict__ x, const float* __restrict__ wp, const float* __restrict__ scale,
-    const float* __restrict__ shift, float* __restrict__ y, float* __restrict__ gap, int Ci, int L,
-    int Co, int nch) {
-  constexpr int S = FC_CC * K / 2;       // MFMA steps per chunk
-  constexpr int PADL = (K - 1) / 2;
-  constexpr int SPAN = FC_TL + K - 1;    // staged positions per row
-  constexpr int NST = (FC_CC * SPAN + FC_T - 1) / FC_T;
-  __shared__ float xs[2][FC_CC * FC_ROW];
-  __shared__ float red[2][FC_COT];
-
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  const int j = lane & 31, h = lane >> 5, wco = wid & 1, wpos = wid >> 1;
-  const int64_t b = blockIdx.x;
-  const int cot = blockIdx.z * 2 + wco;  // this wave's 32-channel tile
-  const bool active = cot * 32 < Co;     // wave-uniform
-  const int ntiles = (L + FC_TL - 1) / FC_TL;
-  const float* xb = x + b * (int64_t)Ci * L;
-  const float* wt = wp + (int64_t)cot * nch * S * 64 + lane;
-
-  // staging map: element e = tid + FC_T i of the chunk's (FC_CC x SPAN) image
-  int st_row[NST], st_t[NST];
-#pragma unroll
-  for (int i = 0; i < NST; ++i) {
-    const int e = tid + FC_T * i;
-    st_row[i] = e / SPAN;
-    st_t[i] = e - st_row[i] * SPAN;
-  }
-
-  float gsum[16];
-#pragma unroll
-  for (int g = 0; g < 16; ++g) gsum[g] = 0.f;
-
-  for (int tile = blockIdx.y; tile < ntiles; tile += gridDim.y) {
-    const int l0 = tile * FC_TL;
-    floatx16 acc0, acc1;
-#pragma unroll
-    for (int g = 0; g < 16; ++g) acc0[g] = acc1[g] = 0.f;
-
-    float st[NST], a[S], an[S];
-    auto stage_load = [&](int c) {
-#pragma unroll
-      for (int i = 0; i < NST; ++i) {
-        const int ci = c * FC_CC + st_row[i], pos = l0 + st_t[i] - PADL;
-        const bool ok = st_row[i] < FC_CC && ci < Ci && pos >= 0 && pos < L;
-        st[i] = ok ? xb[(int64_t)ci * L + pos] : 0.f;
-      }
-    };
-    auto stage_write = [&](int buf) {
-#pragma unroll
-      for (int i = 0; i < NST; ++i)
-        if (st_row[i] < FC_CC) xs[buf][st_row[i] * FC_ROW + st_t[i]] = st[i];
-    };
-
-    stage_load(0);
-    if (active) {
-#pragma unroll
-      for (int s = 0; s < S; ++s) a[s] = wt[s * 64];
-    }
-    stage_write(0);
-    __syncthreads();
-
-    for (int c = 0; c < nch; ++c) {
-      const bool more = c + 1 < nch;
-      if (more) {
-        stage_load(c + 1);
-        if (active) {
-#pragma unroll
-          for (int s = 0; s < S; ++s) an[s] = wt[((int64_t)(c + 1) * S + s) * 64];
-        }
-      }
-      if (active) {
-        const float* xr = xs[c & 1] + wpos * 64 + j;
-#pragma unroll
-        for (int s = 0; s < S; ++s) {
-          const int o0 = ((2 * s) / K) * FC_ROW + (2 * s) % K;
-          const int o1 = ((2 * s + 1) / K) * FC_ROW + (2 * s + 1) % K;
-          const int off = h ? o1 : o0;
-          const float b0 = xr[off], b1 = xr[off + 32];
-          acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a[s], b0, acc0, 0, 0, 0);
-          acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a[s], b1, acc1, 0, 0, 0);
-        }
-      }
-      if (more) {
-        stage_write((c + 1) & 1);
-        if (active) {
-#pragma unroll
-          for (int s = 0; s < S; ++s) a[s] = an[s];
-        }
-      }
-      __syncthreads();  // buffer (c+1)&1 is complete; buffer c&1 is free for chunk c+2
-    }
-
-    if (active) {
-      const int la = l0 + wpos * 64 + j, lb = la + 32;
-#pragma unroll
-      for (int g = 0; g < 16; ++g) {
-        const int co = cot * 32 + (g & 3) + 8 * (g >> 2) + 4 * h;
-        const float sc = scale[co], sh = shift[co];
-        const float va = fmaxf(fmaf(sc, acc0[g], sh), 0.f);
-        const float vb = fmaxf(fmaf(sc, acc1[g], sh), 0.f);
-        if (WY) {
-          float* yr = y + (b * Co + co) * (int64_t)L;
-          if (la < L) yr[la] = va;
-          if (lb < L) yr[lb] = vb;
-        }
-        if (WG) {
-          gsum[g] += la < L ? va : 0.f;
-          gsum[g] += lb < L ? vb : 0.f;
-        }
-      }
-    }
-  }
-
-  if (WG) {
-    if (active) {
-#pragma unroll
-      for (int g = 0; g < 16; ++g) {
-        float v = gsum[g];
-#pragma unroll
-        for (int o = 16; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);  // the 32 columns of a half
-        if (j == 0) red[wpos][wco * 32 + (g & 3) + 8 * (g >> 2) + 4 * h] = v;
-      }
-    }
-    __syncthreads();
-    const int co = blockIdx.z * FC_COT + tid;
-    if (tid < FC_COT && co < Co) gap[b * Co + co] = (red[0][tid] + red[1][tid]) / (float)L;
-  }
-}
-
 template <int K>
 void fcn_conv_launch(const float* x, const float* wp, const float* scale, const float* shift,
                      float* y, float* gap, int64_t B, int Ci, int L, int Co, hipStream_t st) {
@@ -192,13 +39,13 @@ void fcn_conv_launch(const float* x, const float* wp, const float* scale, const 
   const unsigned gz = (unsigned)((Co + FC_COT - 1) / FC_COT);
   TVQ_PLAN("fcn_conv K=%d y=%d gap=%d nch=%d tiles=%d", K, y != nullptr, gap != nullptr, nch, ntiles);
   if (gap && y)
-    hipLaunchKernelGGL((fcn_conv_kernel<K, true, true>), dim3((unsigned)B, 1, gz), dim3(FC_T), 0, st,
+    hipLaunchKernelGGL((fcn_conv_kernel<K, (K - 1) / 2, FC_EP_EVAL, true, true>), dim3((unsigned)B, 1, gz), dim3(FC_T), 0, st,
                        x, wp, scale, shift, y, gap, Ci, L, Co, nch);
   else if (gap)
-    hipLaunchKernelGGL((fcn_conv_kernel<K, false, true>), dim3((unsigned)B, 1, gz), dim3(FC_T), 0,
+    hipLaunchKernelGGL((fcn_conv_kernel<K, (K - 1) / 2, FC_EP_EVAL, false, true>), dim3((unsigned)B, 1, gz), dim3(FC_T), 0,
                        st, x, wp, scale, shift, y, gap, Ci, L, Co, nch);
   else
-    hipLaunchKernelGGL((fcn_conv_kernel<K, true, false>), dim3((unsigned)B, (unsigned)ntiles, gz),
+    hipLaunchKernelGGL((fcn_conv_kernel<K, (K - 1) / 2, FC_EP_EVAL, true, false>), dim3((unsigned)B, (unsigned)ntiles, gz),
                        dim3(FC_T), 0, st, x, wp, scale, shift, y, gap, Ci, L, Co, nch);
 }
 

@@ -9,8 +9,9 @@ trajectory_distances; all 14, the continuous Frechet distance included, on the d
 supervised FCN extractor (reference models/fcn.py) is in through `load_pretrained_FCN`,
 `fcn_features`, `fcn_class_probabilities` and `fcn_inception_score` (fcn_metrics.py; the
 eval forward on the device); the string paths (`Metrics(..., "supervised_fcn")`, the sampler's
-evaluation half, `.inception_score`) still refuse, and FCN training is out of scope, as are
-the flyability evaluation's simulation, filtering and plotting."""
+evaluation half, `.inception_score`) still refuse; the checkpoint it loads is what
+trainers.ExpFCN.save writes.  The flyability evaluation's simulation, filtering and plotting
+are out of scope."""
 from .eval_utils import (calculate_fid, calculate_inception_score, feature_moments,
                          fid_device)
 from .fcn_metrics import (fcn_class_probabilities, fcn_features, fcn_inception_score,

@@ -5,7 +5,8 @@ over positions, nn.Linear.  One `tvq_fcn_conv_bn_relu` launch per block: TensorF
 padding ((K-1)//2 on the left, the rest on the right), the eval BatchNorm folded into a
 per-channel scale / shift applied in the epilogue (not into the weights, so the conv sum is the
 reference's), ReLU; the third launch writes only the pooled features.  `tvq_fcn_head` is the
-final Linear and, on request, the softmax.  Inference only: no autograd.
+final Linear and, on request, the softmax.  Inference only: no autograd here; the training
+step (batch statistics, the backward) is hip/fcn_train.py.
 """
 import torch
 
@@ -87,8 +88,9 @@ def fcn_forward(module, x, return_feature_vector=False, return_probs=False):
     `return_feature_vector`, else the logits, or (logits, softmax) with `return_probs`."""
     if module.training:
         raise NotImplementedError(
-            "FCNBaseline training is not on the HIP path; train it with the reference's "
-            "train_fcn and load the state dict")
+            "FCNBaseline training is not on the HIP path through forward(): the training step "
+            "is FCNBaseline.loss(x, y) (hip.fcn_train.fcn_loss, trainers.ExpFCN); call .eval() "
+            "for the features and logits")
     ptr(x)  # a CPU input is refused before anything runs
     h = x.float().contiguous()
     n = len(module.layers)

@@ -1,16 +1,18 @@
 """FCNBaseline -- the reference's supervised feature extractor (models/fcn.py, from
 arXiv:1909.04939 via okrasolar/pytorch-timeseries) as a parameter holder with the reference's
-state-dict keys, its eval forward on the HIP path (timevqvae.hip.fcn).
+state-dict keys, its eval forward (timevqvae.hip.fcn) and its training step
+(timevqvae.hip.fcn_train) on the HIP path.
 
 ConvBlock(in, 128, 8) -> ConvBlock(128, 256, 5) -> ConvBlock(256, 128, 3) -> mean over
-positions -> Linear(128, classes); every conv is TensorFlow-"same" padded, stride 1.  Training
-(BatchNorm batch statistics, the backward) is not on the HIP path: train with the reference's
-train_fcn and load the state dict.
+positions -> Linear(128, classes); every conv is TensorFlow-"same" padded, stride 1.  `forward`
+is the eval forward and refuses training mode; training goes through `loss(x, y)`, the
+cross-entropy of the training-mode network with its gradients (trainers.ExpFCN drives it).
 """
 import torch
 from torch import nn
 
 from ..hip import fcn as ops
+from ..hip import fcn_train
 
 
 class ConvBlock(nn.Module):
@@ -42,3 +44,16 @@ class FCNBaseline(nn.Module):
         """x (b, c, l) -> logits (b, classes), or the (b, 128) pooled features.  Eval mode
         only (training mode raises NotImplementedError), under no_grad, input cast to fp32."""
         return ops.fcn_forward(self, x, return_feature_vector)
+
+    def loss(self, x: torch.Tensor, y: torch.Tensor):
+        """Training mode: (loss, logits) = (CrossEntropyLoss()(fcn(x), y), fcn(x)) with batch
+        statistics; loss.backward() gives the parameters' gradients and the running statistics
+        are updated (hip.fcn_train.fcn_loss).  y: int64 class indices (b,) or (b, 1)."""
+        return fcn_train.fcn_loss(self, x, y)
+
+    def train(self, mode: bool = True):
+        """nn.Module.train, and the eval path's cached fold of the BatchNorm statistics is
+        dropped: the training kernels and the fused optimizer write through raw pointers, which
+        moves neither `data_ptr` nor `_version`."""
+        self.__dict__.pop("_fcn_fold", None)
+        return super().train(mode)
