@@ -224,16 +224,15 @@ int tvq_conv_out_width(int64_t Win, int64_t KW, int64_t SW, int64_t transposed);
 /* engine selection (process-wide) bits: 1 = halo-tile kernel for fwd/dgrad convs with
  * few gathered channels (whose padded image and weight panel fit in 64 KB of LDS),
  * 2 = halo-tile weight gradient, 4 = halo-tile wherever it fits, 8 = no 32x32-MFMA
- * wide-channel tile, 16 / 32 = its K stage BK = 32 / 16 (default 64), 64 = its 4-wave
- * block (default 12 waves), 128 = its 64-channel variant for narrow maps (default off),
- * 256 = no direct small transposed-gather kernel, 512 = no stride-2 small-channel conv
- * kernels (conv_s2f / conv_s2t), 1024 = no stride-2 small-channel weight-gradient kernel,
- * 2048 = no few-output wide-input kernel (conv_n16: 128 -> <= 16 channels on (B, 128, 3, 32)),
- * 4096 = no stride-2 transposed-gather kernel for the 64 -> 32 and 32 -> 16 channel levels
- * (conv_s2m_t: the ConvTranspose forward and the replicate conv's data gradient);
- * 0 forces the staged GEMMs (with the stride-2 kernels); < 0 only queries.  Default 3.
- * Returns the previous setting. */
-int tvq_conv_config(int64_t halo);
+ * wide-channel tiles (conv_t32 / conv_d32: the tap kernel runs), 512 = no stride-2
+ * small-channel conv kernels (conv_s2f / conv_s2t), 1024 = no stride-2 small-channel
+ * weight-gradient kernel, 4096 = no stride-2 transposed-gather kernel for the 64 -> 32 and
+ * 32 -> 16 channel levels (conv_s2m_t: the ConvTranspose forward and the replicate conv's
+ * data gradient).  Each bit selects a path some test uses as its reference; the product
+ * runs the default, 3.  0 forces the staged GEMMs (with the stride-2 kernels); < 0 only
+ * queries.  Returns the previous setting; any other bit is TVQ_ERR_ARG (tvq_last_error
+ * names it) and leaves the setting unchanged. */
+int tvq_conv_config(int64_t bits);
 /* Block cap of the stride-2 small-channel kernels (conv_s2f / conv_s2t): a launch of S
  * (image, segment) stages runs min(S, cap) blocks, each walking a contiguous run of stages
  * through a two-buffer LDS ring; cap >= S is the one-shot launch (one stage per block).

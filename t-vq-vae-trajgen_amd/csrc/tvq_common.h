@@ -14,8 +14,8 @@ namespace tvq {
 void set_error(const char* fmt, ...);
 
 // k zeroed int32 counters from the current device's pool (tvq_counter_pool), or nullptr
-// when no pool is registered / fused finishes are disabled (TVQ_FUSED_FINISH=0): the
-// caller then falls back to a separate finishing launch.  Slots are handed out round
+// when no pool is registered or the class finishes in a launch of its own (the split-K
+// slabs: FIN_GEMM, FIN_CONV): the caller then runs a separate finishing launch.  Slots are handed out round
 // robin; a kernel returns every counter it used to zero before it exits.
 enum FinishClass { FIN_NORM = 0, FIN_REDUCE = 1, FIN_GEMM = 2, FIN_CONV = 3 };
 int* counters(int64_t k, FinishClass cls);

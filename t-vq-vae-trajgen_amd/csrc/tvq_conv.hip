@@ -67,7 +67,7 @@ static bool launch_conv(int mode, int kind, bool repl, int KK, const float* in, 
     }
   }
   if (launch_small(mode, kind, repl, in, wt, out, g, e, st)) return false;
-  if (ws && g_conv_cfg.n16 && n16_geom_ok(mode, kind, g)) {
+  if (ws && n16_geom_ok(mode, kind, g)) {
     wt = pack_weight(wt, g, KK, ws, st);  // [tap][c][n]
     launch_n16(mode, kind, in, wt, out, g, e, st);
     return e.bn_rv != nullptr;
@@ -98,23 +98,19 @@ static Epi make_epi(const float* bias, const float* residual, float drop_p,
   return e;
 }
 
-extern "C" int tvq_conv_config(int64_t halo) {
+extern "C" int tvq_conv_config(int64_t bits) {
   ConvConfig& c = g_conv_cfg;
-  const int prev = c.halo | (c.t32 ? 0 : 8) | (c.t32_bk == 32 ? 16 : 0) |
-                   (c.t32_bk == 16 ? 32 : 0) | (c.t32_nw == 4 ? 64 : 0) | (c.t32_n64 ? 128 : 0) |
-                   (c.small ? 0 : 256) | (c.s2 ? 0 : 512) | (c.ws2 ? 0 : 1024) |
-                   (c.n16 ? 0 : 2048) | (c.s2m ? 0 : 4096);
-  if (halo >= 0) {
-    c.halo = (int)(halo & 7);
-    c.t32 = (halo & 8) ? 0 : 1;
-    c.t32_bk = (halo & 16) ? 32 : ((halo & 32) ? 16 : 64);
-    c.t32_nw = (halo & 64) ? 4 : 12;
-    c.t32_n64 = (halo & 128) ? 1 : 0;
-    c.small = (halo & 256) ? 0 : 1;
-    c.s2 = (halo & 512) ? 0 : 1;
-    c.ws2 = (halo & 1024) ? 0 : 1;
-    c.n16 = (halo & 2048) ? 0 : 1;
-    c.s2m = (halo & 4096) ? 0 : 1;
+  const int prev = c.halo | (c.t32 ? 0 : 8) | (c.s2 ? 0 : 512) | (c.ws2 ? 0 : 1024) |
+                   (c.s2m ? 0 : 4096);
+  if (bits >= 0) {
+    const int64_t unknown = bits & ~(int64_t)(7 | 8 | 512 | 1024 | 4096);
+    TVQ_CHECK_ARG(unknown == 0, "tvq_conv_config: unknown bit %lld",
+                  (long long)(unknown & -unknown));
+    c.halo = (int)(bits & 7);
+    c.t32 = (bits & 8) ? 0 : 1;
+    c.s2 = (bits & 512) ? 0 : 1;
+    c.ws2 = (bits & 1024) ? 0 : 1;
+    c.s2m = (bits & 4096) ? 0 : 1;
   }
   return prev;
 }

@@ -338,31 +338,16 @@ static int kind_of(int KH, int KW, int SW) {
     }                                                                                    \
   }
 
-// The engine's switches (tvq_conv_config; the object lives in tvq_conv.hip).
-// LDS per conv_t32 block: 2 stages x BK x (128 + 96) floats.  With 12 waves per block, BK = 64
-// (112 KB, 18 barriers for a 3x3 128-channel conv) runs the 128->128 conv at 78.7 us vs
-// 86.7 us for BK = 32 (56 KB); in the joint step, where the LDS is shared with the
-// concurrent streams' kernels, the two are within 0.5 % (7.29 vs 7.25 ms).
-#ifndef TVQ_T32_BK
-#define TVQ_T32_BK 64
-#endif
+// The engine's switches (tvq_conv_config; the object lives in tvq_conv.hip): each selects a
+// path some test uses as its reference.
 struct ConvConfig {
   // bits: 1 = halo fwd/dgrad, 2 = halo wgrad, 4 = halo fwd/dgrad wherever it fits (ignore
   // halo_preferred; tests)
   int halo = 3;
-  int t32 = 1;              // conv_t32 / conv_d32 enabled (bit 8 turns them off)
-  int t32_bk = TVQ_T32_BK;  // conv_t32 K-stage depth: 64, or 32 / 16 (bit 16 / 32)
-  int t32_nw = 12;          // conv_t32 waves per block (12, or 4 with bit 64)
-  // conv_t32's 64-channel tile for narrow maps (bit 128 turns it on).  Off by default:
-  // at the LF band's 64->64 3x3 conv (6144 positions, 64 blocks) it takes 27.5 us against
-  // 23.4 us for the split-K tap kernel + epilogue -- 9 K-stages of 32 MFMAs per wave leave
-  // each stage's load latency exposed; the grid needs split-K or a deeper prefetch.
-  int t32_n64 = 0;
-  int small = 1;  // conv_small_kernel enabled (bit 256 turns it off)
-  int s2 = 1;     // conv_s2f / conv_s2t enabled (bit 512 turns them off)
-  int ws2 = 1;    // conv_wgrad_s2_kernel enabled (bit 1024 turns it off)
-  int n16 = 1;    // conv_n16_kernel enabled (bit 2048 turns it off)
-  int s2m = 1;    // conv_s2m_t enabled (bit 4096 turns it off)
+  int t32 = 1;  // conv_t32 / conv_d32 enabled (bit 8 turns them off)
+  int s2 = 1;   // conv_s2f / conv_s2t enabled (bit 512 turns them off)
+  int ws2 = 1;  // conv_wgrad_s2_kernel enabled (bit 1024 turns it off)
+  int s2m = 1;  // conv_s2m_t enabled (bit 4096 turns it off)
   int s2_cap = 0;  // conv_s2f / conv_s2t block cap (tvq_conv_s2_cap): 0 = the per-kernel default
 };
 const ConvConfig& conv_config();

@@ -419,7 +419,7 @@ bool launch_halo(int mode, int kind, bool repl, const float* in, const float* wt
 template <int MODE, int KH, int KW, int SW, bool REPL>
 static bool launch_small_t(const float* in, const float* wt, float* out, const ConvGeom& g,
                            const Epi& e, hipStream_t st) {
-  if (!(conv_config().small && MODE == GATHER_T && SW == 2 && g.C <= 12 && g.N <= 12)) return false;
+  if (!(MODE == GATHER_T && SW == 2 && g.C <= 12 && g.N <= 12)) return false;
   const int64_t th = (int64_t)g.B * g.Hout * ((g.Wo + 1) / 2);
   // outputs per thread rounded up to 4 (every channel's sum in the same order)
   const dim3 grid((unsigned)((th + 255) / 256));

@@ -3,40 +3,38 @@
 
 namespace tvq {
 
-// Wide-channel implicit GEMM on v_mfma_f32_32x32x2_f32 for the C, N >= 128-class convs
-// (128->128 ResBlock convs at W 32, the Upscale Conv1d pair, their dgrads).  Block tile
-// 128 channels x 96 positions: 4 waves x 32 channels, each wave three 32x32
-// accumulators, so one block per CU covers the 24,576-position maps in 256 blocks
-// without split-K.  K runs tap-major over 64-channel stages (packed weights
-// [tap][c][n], n contiguous -> dwordx4 loads); the next stage is loaded into registers
-// while the current one feeds 96 MFMAs per wave from the other half of a
-// double-buffered LDS tile (112 KB), one barrier per stage.  Loads are raw buffer loads:
-// per-thread offsets are three position bases + compile-time row steps, and an invalid
-// (padding) source gets an offset past the buffer end, which the hardware returns as 0.
-// Each output is the same k-ordered fma chain as conv_tap_kernel's unsplit path
-// (tap-major, channel order within a stage), so the two kernels agree bit for bit.
+// Wide-channel implicit GEMM on v_mfma_f32_32x32x2_f32 for the N % 128 == 0 convs on a full
+// grid (128->128 ResBlock convs at W 32, the Upscale Conv1d pair, the HF band's 16 -> 128
+// forward and 128 -> 16 data gradient).  Block tile 128 channels x 96 positions, 12 waves:
+// wave w owns the 32x32 tile (channels 32 (w % 4), positions 32 (w / 4)), one accumulator,
+// three waves per SIMD so one wave's barrier / address work hides behind the others'
+// MFMAs; one block per CU covers the 24,576-position maps in 256 blocks without split-K.
+// K runs tap-major over BK-channel stages (BK = 64, or 32 / 16 where the channels do not
+// divide 64; packed weights [tap][c][n], n contiguous -> dwordx4 loads).  The first 4
+// waves stage the weights, the other 8 the input; the next stage is loaded into registers
+// while the current one feeds BK / 2 MFMAs per wave from the other half of a
+// double-buffered LDS tile (112 KB at BK = 64), one barrier per stage.  Loads are raw
+// buffer loads: per-thread offsets are three position bases + compile-time row steps, and
+// an invalid (padding) source gets an offset past the buffer end, which the hardware
+// returns as 0.  Each output is the same k-ordered fma chain as conv_tap_kernel's unsplit
+// path (tap-major, channel order within a stage), so the two kernels agree bit for bit.
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t buf_rsrc(const void* p, int64_t bytes) {
   return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0,
                                            (int)(bytes < 0x7fffffff ? bytes : 0x7fffffff),
                                            0x00020000);
 }
 
-// TN = channel tile (128, or 64 for the 64-channel LF convs, whose grids are too small
-// for 128 x 96 tiles and otherwise need split-K); NWN = TN / 32 channel tiles.
-// NW = waves per block: NWN (TN = 128 only: each wave 32 channels x 96 positions, three
-// accumulators) or 3 NWN (each wave one 32x32 tile, up to 3 waves per SIMD so one wave's
-// barrier / address work hides behind the others' MFMAs; the first NWN waves stage the
-// weights, the other 2 NWN the input).  Same k order in every variant.
-template <int MODE, int KH, int KW, int SW, bool REPL, int BK, int NW, int TN, bool POST = false>
-__global__ __launch_bounds__(NW * 64) void conv_t32_kernel(const float* __restrict__ in,
-                                                      const float* __restrict__ wt,
-                                                      float* __restrict__ out, ConvGeom g,
-                                                      Epi e) {
-  constexpr int TM = 96, NWN = TN / 32;
-  constexpr bool SPLIT = NW == 3 * NWN;     // one tile per wave, staging split A | B
-  static_assert(SPLIT || (NW == 4 && TN == 128), "t32 variant");
-  constexpr int ATH = SPLIT ? 64 * NWN : 64 * NW;       // threads loading A
-  constexpr int LB = SPLIT ? 128 * NWN : 64 * NW;       // threads loading B
+// The tile: T32_TN channels x T32_TM positions, T32_NW waves of one 32x32 tile each.
+constexpr int T32_TN = 128, T32_TM = 96, T32_NW = 12;
+
+template <int MODE, int KH, int KW, int SW, bool REPL, int BK, bool POST = false>
+__global__ __launch_bounds__(T32_NW * 64) void conv_t32_kernel(const float* __restrict__ in,
+                                                           const float* __restrict__ wt,
+                                                           float* __restrict__ out, ConvGeom g,
+                                                           Epi e) {
+  constexpr int TM = T32_TM, TN = T32_TN, NWN = TN / 32;
+  constexpr int ATH = 64 * NWN;             // threads loading A (the first NWN waves)
+  constexpr int LB = 128 * NWN;             // threads loading B (the other 2 NWN waves)
   constexpr int ROWF4 = TN / 4;             // dwordx4 per A row (one k)
   constexpr int APASS = ATH / ROWF4;        // A rows per pass (8)
   constexpr int PSTEP = LB % 96;            // position step between a thread's B rows
@@ -49,11 +47,11 @@ __global__ __launch_bounds__(NW * 64) void conv_t32_kernel(const float* __restri
   float* As = smem;                      // [2][BK][TN]
   float* Bs = smem + 2 * BK * TN;        // [2][BK][TM]
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  constexpr int NJ = SPLIT ? 1 : 3;  // 32-position tiles per wave
-  const bool aload = !SPLIT || tid < ATH;
-  const bool bload = !SPLIT || tid >= ATH;
-  const int bt = SPLIT ? tid - ATH : tid;  // index among the B-loading threads
-  const int wch = wid % NWN, wpos = (wid / NWN) * NJ;
+  // this thread stages A | B (two compares: a single flag and its negation compile to
+  // another prologue schedule than the one measured)
+  const bool aload = tid < ATH, bload = tid >= ATH;
+  const int bt = tid - ATH;  // index among the B-loading threads
+  const int wch = wid % NWN, wpos = wid / NWN;
   const int n0 = blockIdx.y * TN, m0 = blockIdx.x * TM;
   const int csteps = g.C / BK;
   const int nsteps = KH * KW * csteps;
@@ -136,11 +134,9 @@ __global__ __launch_bounds__(NW * 64) void conv_t32_kernel(const float* __restri
     }
   };
 
-  floatx16 acc[NJ];
+  floatx16 acc;
 #pragma unroll
-  for (int jb = 0; jb < NJ; ++jb)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[jb][r] = 0.f;
+  for (int r = 0; r < 16; ++r) acc[r] = 0.f;
   const int r32 = lane & 31, hl = lane >> 5;
   load(0);
   store(0);
@@ -151,16 +147,15 @@ __global__ __launch_bounds__(NW * 64) void conv_t32_kernel(const float* __restri
     const float* a = As + buf * BK * TN + hl * TN + wch * 32 + r32;
     const float* bb = Bs + buf * BK * TM + hl * TM + wpos * 32 + r32;
     // fragments of FG k-pairs are read one group ahead of the MFMAs that use them, so
-    // the LDS latency hides behind FG*3 MFMAs instead of stalling every one or two
+    // the LDS latency hides behind FG MFMAs instead of stalling every one or two
     constexpr int FG = 4, NG = BK / 2 / FG;
-    float fa[2][FG], fb[2][FG][NJ];
+    float fa[2][FG], fb[2][FG];
     auto fread = [&](int grp, int slot) {
 #pragma unroll
       for (int u = 0; u < FG; ++u) {
         const int kp = grp * FG + u;
         fa[slot][u] = a[2 * kp * TN];
-#pragma unroll
-        for (int jb = 0; jb < NJ; ++jb) fb[slot][u][jb] = bb[2 * kp * TM + jb * 32];
+        fb[slot][u] = bb[2 * kp * TM];
       }
     };
     fread(0, 0);
@@ -169,20 +164,17 @@ __global__ __launch_bounds__(NW * 64) void conv_t32_kernel(const float* __restri
       if (grp + 1 < NG) fread(grp + 1, (grp + 1) & 1);
 #pragma unroll
       for (int u = 0; u < FG; ++u)
-#pragma unroll
-        for (int jb = 0; jb < NJ; ++jb)
-          acc[jb] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[grp & 1][u], fb[grp & 1][u][jb],
-                                                         acc[jb], 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[grp & 1][u], fb[grp & 1][u], acc, 0, 0, 0);
       // emit the next group's LDS reads ahead of this group's MFMAs (T19)
-      __builtin_amdgcn_sched_group_barrier(0x100, (1 + NJ) * FG, 0);
-      __builtin_amdgcn_sched_group_barrier(0x008, NJ * FG, 0);
+      __builtin_amdgcn_sched_group_barrier(0x100, 2 * FG, 0);
+      __builtin_amdgcn_sched_group_barrier(0x008, FG, 0);
     }
     if (step + 1 < nsteps) store(buf ^ 1);
     __syncthreads();
   }
 
-  // epilogue: acc[jb][reg] = (channel n0 + 32 wch + (reg & 3) + 8 (reg >> 2) + 4 hl,
-  // position m0 + 32 (wpos + jb) + lane % 32); bias, dropout, residual as epi_store
+  // epilogue: acc[reg] = (channel n0 + 32 wch + (reg & 3) + 8 (reg >> 2) + 4 hl,
+  // position m0 + 32 wpos + lane % 32); bias, dropout, residual as epi_store
   const uint64_t seed = e.drop_p > 0.f ? mix_seed(e.seed_ptr, e.offset) : 0ull;
   const int64_t hw = (int64_t)g.Hout * g.Wo;
   PostCh pc[POST ? 16 : 1];  // POST: this lane's 16 channels' BN / Snake terms
@@ -191,116 +183,81 @@ __global__ __launch_bounds__(NW * 64) void conv_t32_kernel(const float* __restri
     for (int r = 0; r < 16; ++r)
       pc[r] = epi_post_ch(e, min(n0 + wch * 32 + (r & 3) + 8 * (r >> 2) + 4 * hl, g.N - 1));
   }
+  const int m = m0 + r32 + wpos * 32;
+  const bool pv = m < g.Mpos;
+  const int mc = pv ? m : 0;
+  const uint32_t bh = fdiv((uint32_t)mc, g.fd_wo);
+  const int w = mc - (int)bh * g.Wo;
+  const int b = (int)fdiv((uint32_t)mc, g.fd_hwo);
+  const int h = (int)bh - b * g.Hout;
+  const int64_t ob = ((int64_t)b * g.N * g.Hout + h) * g.Wo + w;
 #pragma unroll
-  for (int jb = 0; jb < NJ; ++jb) {
-    const int m = m0 + (wpos + jb) * 32 + r32;
-    const bool pv = m < g.Mpos;
-    const int mc = pv ? m : 0;
-    const uint32_t bh = fdiv((uint32_t)mc, g.fd_wo);
-    const int w = mc - (int)bh * g.Wo;
-    const int b = (int)fdiv((uint32_t)mc, g.fd_hwo);
-    const int h = (int)bh - b * g.Hout;
-    const int64_t ob = ((int64_t)b * g.N * g.Hout + h) * g.Wo + w;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int n = n0 + wch * 32 + (r & 3) + 8 * (r >> 2) + 4 * hl;
-      if (!pv || n >= g.N) continue;
-      const int64_t o = ob + (int64_t)n * hw;
-      float v = acc[jb][r] + (e.bias ? e.bias[n] : 0.f);
-      if constexpr (POST) v = epi_post_apply(pc[r], v, e.gelu != 0);
-      if (e.drop_p > 0.f) v = uniform01(seed, (uint64_t)o) >= e.drop_p ? v * e.drop_scale : 0.f;
-      if (e.residual) v += e.residual[o];
-      out[o] = v;
-    }
+  for (int r = 0; r < 16; ++r) {
+    const int n = n0 + wch * 32 + (r & 3) + 8 * (r >> 2) + 4 * hl;
+    if (!pv || n >= g.N) continue;
+    const int64_t o = ob + (int64_t)n * hw;
+    float v = acc[r] + (e.bias ? e.bias[n] : 0.f);
+    if constexpr (POST) v = epi_post_apply(pc[r], v, e.gelu != 0);
+    if (e.drop_p > 0.f) v = uniform01(seed, (uint64_t)o) >= e.drop_p ? v * e.drop_scale : 0.f;
+    if (e.residual) v += e.residual[o];
+    out[o] = v;
   }
 }
 
-// LDS per block: 2 stages x BK x (TN + 96) floats
-static size_t t32_lds(int bk, int tn) { return (size_t)2 * bk * (tn + 96) * 4; }
+// LDS per block: 2 stages x BK x (128 + 96) floats
+static size_t t32_lds(int bk) { return (size_t)2 * bk * (T32_TN + T32_TM) * 4; }
+
+// One launch of the <.., BK, POST> instance.  BK = 64 takes 112 KB of dynamic LDS, which
+// must be opted into once per instance (> 64 KB); BK = 32 / 16 stay under it.
+template <int MODE, int KH, int KW, int SW, bool REPL, int BK, bool POST>
+static void t32_run(unsigned mt, const float* in, const float* wt, float* out, const ConvGeom& g,
+                    const Epi& e, hipStream_t st) {
+  auto* kern = &conv_t32_kernel<MODE, KH, KW, SW, REPL, BK, POST>;
+  if constexpr (BK == 64) {
+    static bool lds_set = false;
+    if (!lds_set) {
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)t32_lds(BK));
+      lds_set = true;
+    }
+  }
+  hipLaunchKernelGGL(kern, dim3(mt, g.N / T32_TN), dim3(64 * T32_NW), t32_lds(BK), st, in, wt,
+                     out, g, e);
+}
 
 // The shapes conv_t32_kernel takes and its launch; false: not its shape.  *post: the
 // epilogue-fused instance ran (it applied e's eval BN / Snake).
 template <int MODE, int KH, int KW, int SW, bool REPL>
 static bool launch_t32_t(const float* in, const float* wt, float* out, const ConvGeom& g,
                          const Epi& e, hipStream_t st, bool* post) {
-  const ConvConfig& cfg = conv_config();
-  // wide channels: 32x32 MFMA tile, no split-K (needs packed weights).  128-channel
-  // tiles on a full grid; 64-channel tiles (6 waves) for N % 64 maps too small for it
-  // (the LF band's 64-channel convs), which otherwise run split-K + an epilogue launch.
-  const bool t32_ok = cfg.t32 && g.wsn == 1 && g.wsc == g.N &&
-                      (int64_t)g.B * g.C * g.Hin * g.Win < (1ll << 29) &&
-                      (int64_t)KH * KW * g.C * g.N < (1ll << 29);
-  const int64_t mt = (g.Mpos + 95) / 96;
-  // K stage: the configured BK where the channels divide it, else 32 / 16 (C = 16 / 48:
-  // the HF band's 16 -> 128 3x3 forward and the 128 -> 16 conv's data gradient, which run
-  // here with a 16 / 32-wide K stage instead of on the halo tile: 32.2 / 30.9 -> 22.1 /
-  // 20.3 us, step -30 us)
-  const int bk = g.C % cfg.t32_bk == 0 ? cfg.t32_bk : (g.C % 32 == 0 ? 32 : 16);
-  const bool wide128 = t32_ok && g.N % 128 == 0 && mt * (g.N / 128) >= 192;
-  const bool wide64 = !wide128 && t32_ok && cfg.t32_n64 && g.C % 64 == 0 && g.N % 64 == 0 &&
-                      mt >= 32;
-  if (!wide128 && !wide64) return false;
-  static bool lds_set = false;  // > 64 KB of dynamic LDS must be opted into once
-  if (!lds_set) {
-    (void)hipFuncSetAttribute(
-        reinterpret_cast<const void*>(&conv_t32_kernel<MODE, KH, KW, SW, REPL, 64, 4, 128>),
-        hipFuncAttributeMaxDynamicSharedMemorySize, (int)t32_lds(64, 128));
-    (void)hipFuncSetAttribute(
-        reinterpret_cast<const void*>(&conv_t32_kernel<MODE, KH, KW, SW, REPL, 64, 12, 128>),
-        hipFuncAttributeMaxDynamicSharedMemorySize, (int)t32_lds(64, 128));
-    (void)hipFuncSetAttribute(
-        reinterpret_cast<const void*>(&conv_t32_kernel<MODE, KH, KW, SW, REPL, 64, 6, 64>),
-        hipFuncAttributeMaxDynamicSharedMemorySize, (int)t32_lds(64, 64));
-    lds_set = true;
-  }
-#define TVQ_T32(BKV, NWV, TNV)                                                             \
-  hipLaunchKernelGGL((conv_t32_kernel<MODE, KH, KW, SW, REPL, BKV, NWV, TNV>),             \
-                 dim3((unsigned)mt, g.N / TNV), dim3(64 * NWV), t32_lds(BKV, TNV), st, in, \
-                 wt, out, g, e)
-  // eval conv -> BN (-> Snake / after GELU): the epilogue-fused instance (12 waves, 128
-  // channels; Upscale's Conv1d, the 128-channel ResBlock convs)
+  // wide channels on a full grid: 32x32 MFMA tile, no split-K (needs packed weights)
+  const unsigned mt = (unsigned)((g.Mpos + T32_TM - 1) / T32_TM);
+  if (!(conv_config().t32 && g.wsn == 1 && g.wsc == g.N &&
+        (int64_t)g.B * g.C * g.Hin * g.Win < (1ll << 29) &&
+        (int64_t)KH * KW * g.C * g.N < (1ll << 29) && g.N % T32_TN == 0 &&
+        (int64_t)mt * (g.N / T32_TN) >= 192))
+    return false;
+  // K stage: 64 where the channels divide it, else 32 / 16 (C = 16 / 48: the HF band's
+  // 16 -> 128 3x3 forward and the 128 -> 16 conv's data gradient)
+  const int bk = g.C % 64 == 0 ? 64 : (g.C % 32 == 0 ? 32 : 16);
+#define TVQ_T32(POSTV)                                                                   \
+  if (bk == 64) t32_run<MODE, KH, KW, SW, REPL, 64, POSTV>(mt, in, wt, out, g, e, st);      \
+  else if (bk == 32) t32_run<MODE, KH, KW, SW, REPL, 32, POSTV>(mt, in, wt, out, g, e, st); \
+  else t32_run<MODE, KH, KW, SW, REPL, 16, POSTV>(mt, in, wt, out, g, e, st)
+  // eval conv -> BN (-> Snake / after GELU): the epilogue-fused instance (Upscale's
+  // Conv1d, the 128-channel ResBlock convs, the HF encoder's 16 -> 128 conv)
   constexpr bool t32_post = MODE == GATHER_F && !REPL &&
                             ((KH == 1 && KW == 3) || (KH == 3 && KW == 3));
   if constexpr (t32_post) {
-    if (e.bn_rv && !wide64 && cfg.t32_nw == 12) {
-      static bool lds_post = false;
-      if (!lds_post) {
-        (void)hipFuncSetAttribute(
-            reinterpret_cast<const void*>(
-                &conv_t32_kernel<MODE, KH, KW, SW, REPL, 64, 12, 128, true>),
-            hipFuncAttributeMaxDynamicSharedMemorySize, (int)t32_lds(64, 128));
-        lds_post = true;
-      }
+    if (e.bn_rv) {
       TVQ_PLAN("conv_t32 bk%d nw12 tn128 post", bk);
-      if (bk == 64)
-        hipLaunchKernelGGL((conv_t32_kernel<MODE, KH, KW, SW, REPL, 64, 12, 128, true>),
-                           dim3((unsigned)mt, g.N / 128), dim3(64 * 12), t32_lds(64, 128), st,
-                           in, wt, out, g, e);
-      else if (bk == 32)
-        hipLaunchKernelGGL((conv_t32_kernel<MODE, KH, KW, SW, REPL, 32, 12, 128, true>),
-                           dim3((unsigned)mt, g.N / 128), dim3(64 * 12), t32_lds(32, 128), st,
-                           in, wt, out, g, e);
-      else  // the 16-channel -> 128 convs (HF encoder's last ResBlock)
-        hipLaunchKernelGGL((conv_t32_kernel<MODE, KH, KW, SW, REPL, 16, 12, 128, true>),
-                           dim3((unsigned)mt, g.N / 128), dim3(64 * 12), t32_lds(16, 128), st,
-                           in, wt, out, g, e);
+      TVQ_T32(true);
       *post = true;
       return true;
     }
   }
-  TVQ_PLAN("conv_t32 bk%d nw%d tn%d", wide64 ? 64 : bk, wide64 ? 6 : cfg.t32_nw,
-           wide64 ? 64 : 128);
-  if (wide64) {
-    TVQ_T32(64, 6, 64);
-  } else if (cfg.t32_nw == 12) {
-    if (bk == 64) TVQ_T32(64, 12, 128);
-    else if (bk == 16) TVQ_T32(16, 12, 128);
-    else TVQ_T32(32, 12, 128);
-  } else {
-    if (bk == 64) TVQ_T32(64, 4, 128);
-    else if (bk == 16) TVQ_T32(16, 4, 128);
-    else TVQ_T32(32, 4, 128);
-  }
+  TVQ_PLAN("conv_t32 bk%d nw12 tn128", bk);
+  TVQ_T32(false);
 #undef TVQ_T32
   return true;
 }

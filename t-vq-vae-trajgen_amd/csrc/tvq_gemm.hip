@@ -240,7 +240,7 @@ static int gemm_splits(int M, int N, int K, int tiles) {
 
 using namespace tvq;
 
-// Largest tile that still gives >= TVQ_GEMM_MIN_BLOCKS (default 256) blocks: the GEMMs
+// Largest tile that still gives >= gemm_min_blocks() (256) blocks: the GEMMs
 // here have K <= 512, so filling the 256 CUs matters more than tile reuse.  (Measured:
 // 1024 / 2048 minimum blocks, i.e. smaller tiles, change neither the sampler's
 // M = 25600, N = 128, K = 128 projections nor the train step.)  Deep-K GEMMs that stay

@@ -90,7 +90,7 @@ class GraphedSampler:
         # replay instead of one pack launch per conv (the weights are fixed within a batch)
         self.packs = PackCache(self.device)
         # the LF decoder needs only the final LF tokens: it runs on a side stream while the
-        # HF prior's pass and the HF decoder run (TVQ_SAMPLER_OVERLAP=0: one stream)
+        # HF prior's pass and the HF decoder run (one stream on a device without streams)
         overlap = self.device.type == "cuda"
         self._side = torch.cuda.Stream(self.device) if overlap else None
 

@@ -97,7 +97,7 @@ def _conv_case(kind, Ci, Co, W, cuda, want_fwd=None, want_dgrad=None, want_wgrad
 
 def test_conv_16_to_128_fwd_on_t32_bk16(cuda):
     """HF ResBlock(16 -> 128) first conv on (256, 16, 3, 32): forward on conv_t32 with a
-    16-wide K stage (tvq_conv_t32.hip launch_t32, 'wide128' with bk 16)."""
+    16-wide K stage (tvq_conv_t32.hip launch_t32_t: bk 16, the stage of 16 gathered channels)."""
     _conv_case("res", 16, 128, 32, cuda, want_fwd="conv_t32 bk16")
 
 

@@ -818,63 +818,83 @@ def test_conv_direct_narrow_maps(Ci, Co, KH, KW, SW, rep, W, cuda):
     torch.testing.assert_close(outs[0], outs[1], rtol=1e-5, atol=1e-5)
 
 
-@pytest.mark.parametrize("op", ["fwd", "dgrad", "conv1d_fwd", "conv1d_dgrad", "fwd64", "dgrad64",
-                                "fwd128n", "dgrad128n"])
+@pytest.mark.parametrize("op", ["fwd", "dgrad", "conv1d_fwd", "conv1d_dgrad", "fwd_c32", "fwd_c16",
+                                "dgrad_c32", "dgrad_c16"])
 def test_conv_wide_tile_matches_tap(op, cuda):
-    """The 32x32-MFMA wide-channel tile (C, N >= 128 on a full grid) computes each output as
+    """The 32x32-MFMA wide-channel tile (N % 128 == 0 on a full grid) computes each output as
     the same k-ordered fma chain as the tap-major kernel's unsplit path: bitwise equal to it,
-    and within the fp32 tolerance of torch's CPU conv."""
-    from timevqvae.hip._native import call, ptr, stream_ptr, value
+    and within the fp32 tolerance of torch's CPU conv.  The K stage follows the gathered
+    channels alone: 64 where they divide it, else 32 / 16 (the _c32 / _c16 cases: 32 / 16 ->
+    128 forward, the data gradient of a 128 -> 32 / 16 conv).  B = 192 on (3, 32) is the
+    smallest such batch with 192 tiles of 96 positions x 128 channels, the wide tile's
+    threshold.  The dispatch trace pins which kernel each run took."""
+    from timevqvae.hip._native import call, plan_trace, ptr, stream_ptr, value
     gen = torch.Generator().manual_seed(11)
+    B, Ci, Co, H, W, KH, KW = 192, 128, 128, 3, 32, 3, 3
     if op.startswith("conv1d"):
         B, Ci, Co, H, W, KH, KW = 256, 128, 256, 1, 96, 1, 3
-    elif op.endswith("64"):  # LF band 64-channel ResBlock conv: the 64-channel tile
-        B, Ci, Co, H, W, KH, KW = 256, 64, 64, 3, 8, 3, 3
-    elif op.endswith("128n"):  # 128 channels on a narrow map: 64-channel tile, 2 column tiles
-        B, Ci, Co, H, W, KH, KW = 256, 128, 128, 3, 8, 3, 3
-    else:
-        B, Ci, Co, H, W, KH, KW = 192, 128, 128, 3, 32, 3, 3
+    elif op.startswith("fwd_c"):
+        Ci = int(op[5:])
+    elif op.startswith("dgrad_c"):
+        Co = int(op[7:])
+    red = Ci if "fwd" in op else Co  # the gathered (reduction) channels
+    bk = 64 if red % 64 == 0 else (32 if red % 32 == 0 else 16)
     x = torch.randn(B, Ci, H, W, generator=gen)
     w = torch.randn(Co, Ci, KH, KW, generator=gen) * 0.05
     bias = torch.randn(Co, generator=gen)
     dy = torch.randn(B, Co, H, W, generator=gen)
     xd, wd, bd, dyd = x.to(cuda), w.to(cuda), bias.to(cuda), dy.to(cuda)
-    outs = []
+    outs, traces = [], []
     prev = value("tvq_conv_config", -1)
     try:
-        # wide tile (packed) at K-stage depth BK = 64, 32, 16, with 12 and 4 waves per block
-        # | tap, unsplit, raw
-        # (128: the 64-channel variant, which is what the narrow "64"/"128n" maps exercise;
-        # without it those maps run the split-K tap kernel, a different summation order)
-        cfgs = ((0, True), (16, True), (32, True), (64, True), (80, True), (8, False))
-        if op.endswith(("64", "128n")):
-            cfgs = ((128, True), (8, False))
-        for cfg, use_ws in cfgs:
+        # wide tile (packed weights) | tap, unsplit, raw
+        for cfg, use_ws in ((0, True), (8, False)):
             value("tvq_conv_config", cfg)
-            if "fwd" in op:
-                y = torch.empty(B, Co, H, W, device=cuda)
-                ws = torch.empty(value("tvq_conv_workspace", 0, B, Ci, H, W, Co, KH, KW, 1, 0),
-                                 device=cuda) if use_ws else None
-                call("tvq_conv2d_fwd", ptr(xd), B, Ci, H, W, ptr(wd), ptr(bd), Co, KH, KW, 1, 0,
-                     ptr(y), None, 0.0, None, 0, ptr(ws), stream_ptr())
-            else:
-                y = torch.empty(B, Ci, H, W, device=cuda)
-                ws = torch.empty(value("tvq_conv_workspace", 2, B, Ci, H, W, Co, KH, KW, 1, 0),
-                                 device=cuda) if use_ws else None
-                call("tvq_conv2d_dgrad", ptr(dyd), B, Co, H, W, ptr(wd), Ci, KH, KW, 1, 0, ptr(y),
-                     W, ptr(ws), stream_ptr())
+            with plan_trace() as tr:
+                if "fwd" in op:
+                    y = torch.empty(B, Co, H, W, device=cuda)
+                    ws = torch.empty(value("tvq_conv_workspace", 0, B, Ci, H, W, Co, KH, KW, 1, 0),
+                                     device=cuda) if use_ws else None
+                    call("tvq_conv2d_fwd", ptr(xd), B, Ci, H, W, ptr(wd), ptr(bd), Co, KH, KW, 1, 0,
+                         ptr(y), None, 0.0, None, 0, ptr(ws), stream_ptr())
+                else:
+                    y = torch.empty(B, Ci, H, W, device=cuda)
+                    ws = torch.empty(value("tvq_conv_workspace", 2, B, Ci, H, W, Co, KH, KW, 1, 0),
+                                     device=cuda) if use_ws else None
+                    call("tvq_conv2d_dgrad", ptr(dyd), B, Co, H, W, ptr(wd), Ci, KH, KW, 1, 0, ptr(y),
+                         W, ptr(ws), stream_ptr())
             outs.append(y)
+            traces.append(tr)
     finally:
         value("tvq_conv_config", prev)
     torch.cuda.synchronize()
-    for o in outs[:-1]:
-        assert torch.equal(o, outs[-1])
+    assert traces[0].has(f"conv_t32 bk{bk} "), traces[0].lines
+    assert not traces[1].has("conv_t32"), traces[1].lines
+    assert torch.equal(outs[0], outs[1])
     pad = (KH // 2, (KW - 1) // 2)
     if "fwd" in op:
         ref = F.conv2d(x, w, bias, padding=pad)
     else:
         ref = torch.nn.grad.conv2d_input(x.shape, w, dy, padding=pad)
     close(outs[0].cpu(), ref, what=op)
+
+
+def test_conv_config_rejects_unknown_bits(cuda):
+    """tvq_conv_config takes the bits 1, 2, 4, 8, 512, 1024 and 4096; any other is an argument
+    error that names the bit and leaves the setting as it was."""
+    from timevqvae.hip._native import lib, value
+    prev = value("tvq_conv_config", -1)
+    try:
+        assert value("tvq_conv_config", 16) == -1
+        assert "16" in lib().tvq_last_error().decode()
+        assert value("tvq_conv_config", -1) == prev
+        assert value("tvq_conv_config", 8 | 2048) == -1
+        assert "2048" in lib().tvq_last_error().decode()
+        assert value("tvq_conv_config", -1) == prev
+        assert value("tvq_conv_config", 7 | 8 | 512 | 1024 | 4096) == prev
+        assert value("tvq_conv_config", -1) == 7 | 8 | 512 | 1024 | 4096
+    finally:
+        value("tvq_conv_config", prev)
 
 
 @pytest.mark.gpu

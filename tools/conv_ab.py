@@ -1,5 +1,6 @@
-"""Time one conv (fwd and dgrad) under two tvq_conv_config settings, weights from a pack
-cache scope (as in the step).  usage: python tools/conv_ab.py B Ci Co H W cfgA cfgB"""
+"""Time one conv (fwd and dgrad) under two tvq_conv_config settings (its bits: include/tvq.h),
+weights from a pack cache scope (as in the step).
+usage: python tools/conv_ab.py B Ci Co H W cfgA cfgB"""
 import os
 import sys
 
@@ -19,7 +20,8 @@ def main():
     w.requires_grad_(True)
     b = torch.zeros(Co, device=dev)
     for cfg in (ca, cb, ca, cb):
-        value("tvq_conv_config", cfg)
+        if value("tvq_conv_config", cfg) < 0:
+            raise SystemExit(f"tvq_conv_config({cfg}): not a setting (include/tvq.h lists the bits)")
         pc = PackCache(dev, 1 << 20)
         with pc.scope():
             y = conv2d(x, w, b)
